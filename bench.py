@@ -3,7 +3,8 @@
 (BASELINE.json configs[1]).  One step = model(batch, return_loss=False) on one tile whose points are
 already resident in HBM: voxel hashing, all 13 rulebooks, 65 sparse convs, heads.
 
-    python bench.py --gpus N --steps K --warmup W [--dtype bf16|fp32] [--workload config2|config4|config5]
+    python bench.py --gpus N --steps K --warmup W [--dtype bf16|fp32] [--workload config2|config3|config4|config5]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU)
 
 With --gpus N > 1 and no launcher environment (WORLD_SIZE unset) this process only SPAWNS the N ranks
@@ -12,8 +13,14 @@ JSON line and exits with the children's status.
 
 Multi-GPU: tiles are independent -> every rank runs its own tile, no data-path
 collective; weak scaling; value = points processed by all ranks / max-over-ranks time.
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = the gather-GEMM conv, timed live with
-HIP events) and `cpu_baseline` (the oracle port on the host cores, bounded sample).
+
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (wall time of one timed step) and the workload's `config`.
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (see dump_outputs).
+--full adds everything else the line used to carry: `roofline` (dominant kernel = the gather-GEMM conv, timed live with
+HIP events), one-tile-at-a-time and latency figures, the fp32 / bf16x3 parity modes, the config-3 / 4 / 5 ride-along
+blocks, the power sample, `cpu_baseline` (the oracle port on the host cores, bounded sample), and with N > 1 the sharded
+plot and the collective check.
 """
 import argparse
 import json
@@ -32,6 +39,32 @@ sys.path.insert(0, REPO)
 PEAK_MFMA_F32_TFLOPS = 157.3       # MI355X_MICROARCH.md: fp32-input MFMA = vector rate
 PEAK_MFMA_BF16_TFLOPS = 2500.0     # dense
 PEAK_HBM_GBS = 8000.0
+DUMP_BUDGET_BYTES = 64_000_000     # --dump-outputs: at most this much in all, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write `arrays` (name -> tensor / array / list, what the timed path returned in its last step) as
+    out_dir/<name>.npy, float32, or float64 where the values are 64-bit floats or integers (labels, losses).  Past
+    DUMP_BUDGET_BYTES in all, every array of more than 1 MB keeps the same fraction of its rows, a fixed seeded subset in
+    ascending order (the prefix of one seeded permutation per row count), so two builds run with the same arguments compare
+    row for row; smaller arrays are written whole."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: torch.as_tensor(v).detach() for k, v in arrays.items()}
+    wide = lambda t: t.dtype in (torch.float64, torch.int64, torch.int32)                       # noqa: E731
+    size = {k: t.numel() * (8 if wide(t) else 4) for k, t in arrays.items()}
+    big = {k for k, b in size.items() if b > (1 << 20)}
+    big_bytes = sum(size[k] for k in big)
+    room = DUMP_BUDGET_BYTES - 4096 * len(arrays) - sum(size.values()) + big_bytes                   # (4 KB per file for its header)
+    frac = min(1.0, room / big_bytes) if big_bytes else 1.0
+    perms = {}
+    for name, t in arrays.items():
+        if frac < 1.0 and name in big:
+            n = t.shape[0]
+            if n not in perms:
+                perms[n] = np.random.default_rng(0).permutation(n)
+            rows = np.sort(perms[n][:int(n * frac)])
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float64 if wide(t) else torch.float32).cpu().numpy())
 
 
 def conv_work(meta):
@@ -207,11 +240,16 @@ def pmc_traffic(dtype, workload):
     return best
 
 
+PLOT_RESULTS = ("semantic_prediction_logits", "semantic_labels", "offset_predictions", "offset_labels", "coords", "instance_labels",
+                "backbone_feats", "input_feats")                    # the 8 per-point arrays of get_pointwise_preds(_sharded), in order
+
+
 def sharded_plot(model, dist, rank, world, n_tiles, steps, warmup):
     """BASELINE config 4: `n_tiles` overlapping-tile forwards of one plot sharded over the ranks (round-robin = LPT on equal
     tiles), every rank materialising only its own tiles, inputs resident in HBM; one step = the whole plot through
     util.sharding.get_pointwise_preds_sharded: per-rank tile loop (inner-square filter on the device) + the two collectives of
-    the record gather INSIDE the timed region.  Returns (seconds per plot (max over ranks), total points, gathered rows)."""
+    the record gather INSIDE the timed region.  Returns (seconds per plot (max over ranks), total points, gathered rows, the last
+    plot's 8 result arrays on the device)."""
     from treelearn_amd.synth import PLOT4, make_plot, plot_squares
     from treelearn_amd.util.sharding import TileList, assign_tiles, get_pointwise_preds_sharded
     from treelearn_amd.util.tiles import PlotTiler
@@ -246,7 +284,7 @@ def sharded_plot(model, dist, rank, world, n_tiles, steps, warmup):
     torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
     dt = torch.tensor([time.perf_counter() - t0], device="cuda", dtype=torch.float64)
     dist.all_reduce(dt, op=dist.ReduceOp.MAX)
-    return float(dt) / steps, int(npts.sum()), int(out[0].shape[0])
+    return float(dt) / steps, int(npts.sum()), int(out[0].shape[0]), out
 
 
 def host_resident_tile_loop(model, n_tiles=16, reps=3):
@@ -335,13 +373,21 @@ def training_step_bench(args, rank, world, dist):
     dt = float(tmax)
     if rank != 0:
         return None
-    # algorithmic conv flops of one step: forward + dgrad + wgrad = 3 x (2 * pairs * Cin * Cout) over the 71 conv launches
-    model.eval()
-    fl = sum(conv_work(m)[0] for _, m in conv_event_pass(model, gb, 1)[0])
-    model.train()
     sec = dt / args.steps
-    peak = PEAK_MFMA_F32_TFLOPS if args.dtype == "fp32" else PEAK_MFMA_BF16_TFLOPS
-    ach = 3.0 * fl / sec / 1e12
+    if getattr(args, "dump_outputs", None):
+        # what the caller of the step holds after the last one: the loss values it read and the parameters AdamW wrote
+        dump_outputs(args.dump_outputs, dict(losses=np.asarray(vals, np.float64),
+                                             parameters=torch.cat([p_.detach().reshape(-1).float() for p_ in model.parameters()])))
+    roof = None
+    if args.full:
+        # algorithmic conv flops of one step: forward + dgrad + wgrad = 3 x (2 * pairs * Cin * Cout) over the 71 conv launches
+        model.eval()
+        fl = sum(conv_work(m)[0] for _, m in conv_event_pass(model, gb, 1)[0])
+        model.train()
+        peak = PEAK_MFMA_F32_TFLOPS if args.dtype == "fp32" else PEAK_MFMA_BF16_TFLOPS
+        ach = 3.0 * fl / sec / 1e12
+        roof = dict(bound="mfma", achieved=ach, peak=peak, unit="TFLOP/s", frac=ach / peak, traffic=None,
+                    note="algorithmic conv flops of the step (forward + dgrad + wgrad = 3 x 2 * pairs * Cin * Cout) / whole step time")
     return dict(metric="Mpoints/sec through sparse U-Net training step (fwd + bwd + AdamW; 0.1 m voxel, 2 x 40x40 m crops)",
                 value=float(npts) / sec / 1e6, unit="Mpoints/s", n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=sec * 1e3,
                 higher_is_better=True, scaling="weak", vs_baseline=None, dtype=args.dtype, data="synthetic",
@@ -349,9 +395,7 @@ def training_step_bench(args, rank, world, dist):
                                      f"(30.1 M params, random init), torch.optim.AdamW({'fused=True' if fused else 'for-each'}), grad-norm clip 1.0, " + {"bf16": "bf16 mixed precision (autocast-like)", "fp32": "fp32", "fp16":
                             "float16 autocast + GradScaler (the reference's regime, tools/training/train.py:32,40-44)"}.get(args.dtype, args.dtype),
                             points_per_step=n_pts, last_losses=vals, **(dict(gradscaler_skipped_steps=skipped[0], gradscaler_final_scale=scaler.get_scale()) if fp16 else {})),
-                roofline=dict(bound="mfma", achieved=ach, peak=peak, unit="TFLOP/s", frac=ach / peak, traffic=None,
-                              note="algorithmic conv flops of the step (forward + dgrad + wgrad = 3 x 2 * pairs * Cin * Cout) / whole step time"),
-                cpu_baseline=None)
+                roofline=roof, cpu_baseline=None)
 
 
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "fp32": torch.float32, "bf16x3": "bf16x3"}     # bf16x3: fp32 storage, split-bf16 contraction
@@ -477,8 +521,17 @@ def main():
     ap.add_argument("--workload", default="config2", choices=["config2", "config3", "config4", "config5"])
     ap.add_argument("--plot-tiles", type=int, default=64, help="config4: tiles of the plot")
     ap.add_argument("--no-sharded-plot", action="store_true", help="N > 1: skip the config-4 sharded tile loop + gather measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (roofline, latency, parity modes, ride-along workloads, "
+                         "power, CPU baseline, the N > 1 sharded plot); the --no-* switches and --layer-table act within it")
     ap.add_argument("--cpu-baseline-worker", action="store_true")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.layer_table and not args.full:
+        ap.error("--layer-table comes from the conv event pass of --full")
     if args.cpu_baseline_worker:
         print(json.dumps(cpu_baseline_worker()), flush=True)
         return
@@ -529,7 +582,10 @@ def main():
                           compute_dtype=DTYPES[args.dtype])
         model.load_state_dict(random_state_dict(7, channels=32, num_blocks=7), strict=True)
         model = model.cuda().eval()
-        sec, total_pts, rows = sharded_plot(model, dist, rank, world, args.plot_tiles, args.steps, args.warmup)
+        sec, total_pts, rows, out = sharded_plot(model, dist, rank, world, args.plot_tiles, args.steps, args.warmup)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {k: t for k, t in zip(PLOT_RESULTS, out) if t.numel()})
+        del out
         if rank == 0:
             res = dict(metric="Mpoints/sec through sparse U-Net fwd (0.1 m voxel, 40x40 m tile)", value=total_pts / sec / 1e6, unit="Mpoints/s",
                        n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=sec * 1e3, higher_is_better=True, scaling="strong",
@@ -590,11 +646,14 @@ def main():
     if dist: dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run_steps(args.steps)
+    last = run_steps(args.steps)
     torch.cuda.synchronize()
     if dist: dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)                          # the dict of the last timed forward (before any later forward runs)
+    del last
     tmax = torch.tensor([dt], device="cuda", dtype=torch.float64)
     npts = torch.tensor([float(n_pts)], device="cuda", dtype=torch.float64)
     if dist:
@@ -604,7 +663,7 @@ def main():
 
     # live per-kernel timing of the conv launches (separate pass: event pairs perturb the pipeline)
     roof = None
-    if rank == 0:
+    if rank == 0 and args.full:
         reps = 3
         passes = conv_event_pass(model, gbatch, reps)
         per = len(passes[0])
@@ -661,6 +720,7 @@ def main():
         if share or backend != "nccl":
             res["config"]["test_mode"] = f"ranks share GPU 0 / backend {backend}: a plumbing test of the N > 1 flow, not a measurement"
 
+    if rank == 0 and args.full:
         if nfl > 1:                                                    # the same forward strictly one tile after the other, for reference
             with torch.no_grad():
                 for _ in range(2): step()
@@ -716,11 +776,11 @@ def main():
             # one run carries them: the training step (config 3) and the 0.05 m stress tile (config 5)
             import types
             try:
-                ts = training_step_bench(types.SimpleNamespace(steps=8, warmup=3, dtype=args.dtype), 0, 1, None)
+                ts = training_step_bench(types.SimpleNamespace(steps=8, warmup=3, dtype=args.dtype, full=True), 0, 1, None)
                 res["training_step"] = {k: ts[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "dtype", "config", "roofline")}
                 if args.dtype == "bf16":
                     # the reference's own regime beside it: float16 autocast + GradScaler on the float16 training kernels
-                    t16 = training_step_bench(types.SimpleNamespace(steps=6, warmup=3, dtype="fp16"), 0, 1, None)
+                    t16 = training_step_bench(types.SimpleNamespace(steps=6, warmup=3, dtype="fp16", full=True), 0, 1, None)
                     res["training_step"]["fp16_autocast_gradscaler"] = dict(ms_per_step=t16["ms_per_step"], value=t16["value"], unit=t16["unit"],
                                                                             gradscaler_skipped_steps=t16["config"]["gradscaler_skipped_steps"],
                                                                             gradscaler_final_scale=t16["config"]["gradscaler_final_scale"], last_losses=t16["config"]["last_losses"])
@@ -747,7 +807,7 @@ def main():
                 os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", str(_free_port()))
                 d4.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", local))
                 used_rccl_extra = True
-                sec4, tp4, rows4 = sharded_plot(model, d4, 0, 1, args.plot_tiles, 1, 1)
+                sec4, tp4, rows4, _ = sharded_plot(model, d4, 0, 1, args.plot_tiles, 1, 1)
                 res["config4"] = dict(value=tp4 / sec4 / 1e6, unit="Mpoints/s", ms_per_plot=sec4 * 1e3, ms_per_tile=sec4 * 1e3 / args.plot_tiles, tiles=args.plot_tiles,
                                       total_points=tp4, gathered_rows=rows4, collectives_per_plot=2, n_gpus=1, dtype=args.dtype,
                                       workload=f"config4: whole-plot inference, {args.plot_tiles} overlapping 40x40 m tiles (voxel 0.1 m, 8 m inner squares every 4 m) of ONE synthetic plot through "
@@ -768,13 +828,13 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
             res["config"]["cpu_baseline_sample"] = "26x26 m tile of the same generator / voxel size / model (about 40 % of the points of the timed tile), 1 forward"
-    if dist and (world > 1 or os.environ.get("TL_BENCH_FORCE_DIST") == "1") and args.workload == "config2" and not args.no_sharded_plot:
+    if args.full and dist and (world > 1 or os.environ.get("TL_BENCH_FORCE_DIST") == "1") and args.workload == "config2" and not args.no_sharded_plot:
         # BASELINE config 4 alongside: 8 tiles per rank through the sharded tile loop WITH the record gather timed (weak form of the
         # 64-tiles-on-8-GPUs plot; `--workload config4` times the fixed 64-tile plot instead)
         # (a ride-along block: the headline above is already measured, so a failure here -- this is the one flow no 1-GPU box can rehearse with RCCL
         # across devices -- is reported in the line instead of costing the line)
         try:
-            sec, tp, rows = sharded_plot(model, dist, rank, world, 8 * world, 2, 1)
+            sec, tp, rows, _ = sharded_plot(model, dist, rank, world, 8 * world, 2, 1)
             if rank == 0:
                 res["sharded_plot"] = dict(value=tp / sec / 1e6, unit="Mpoints/s", tiles=8 * world, ms_per_plot=sec * 1e3, gathered_rows=rows,
                                            collectives_per_plot=2, note="tile loop + inner-square filter + device-resident record gather, timed together")
@@ -782,12 +842,13 @@ def main():
             if rank == 0:
                 res["sharded_plot"] = dict(error=f"{type(e).__name__}: {e}"[:400])
     if dist:
-        # proof that the collective library saw `world` ranks: an all-reduce of ones over the group the timing barriers used
+        # --full: proof that the collective library saw `world` ranks, an all-reduce of ones over the group the timing barriers used
         try:
-            one = torch.ones(1, device="cuda", dtype=torch.float32)
-            dist.all_reduce(one)
-            if rank == 0:
-                res["rccl_world"] = int(round(float(one)))
+            if args.full:
+                one = torch.ones(1, device="cuda", dtype=torch.float32)
+                dist.all_reduce(one)
+                if rank == 0:
+                    res["rccl_world"] = int(round(float(one)))
             dist.destroy_process_group()
         except Exception as e:                                         # noqa: BLE001
             if rank == 0:

@@ -701,10 +701,10 @@ def test_feature_buffers_beyond_2g_and_4g_bytes(dt, n_in, cin, cout):
 
 # ------------------------------------------------------------------------------------------------ bench.py itself
 @pytest.mark.parametrize("flags", [
-    ["--workload", "config2", "--steps", "3", "--warmup", "1"],
-    ["--workload", "config3", "--steps", "1", "--warmup", "1"],
+    ["--workload", "config2", "--steps", "3", "--warmup", "1", "--full"],               # --full: the ride-along blocks and the roofline pass too
+    ["--workload", "config3", "--steps", "1", "--warmup", "1", "--full"],
     ["--workload", "config4", "--plot-tiles", "3", "--steps", "2", "--warmup", "1"],
-    ["--workload", "config2", "--steps", "2", "--warmup", "1", "FORCE_DIST"],          # the N > 1 code path (RCCL group + the sharded-plot extra) on one GPU
+    ["--workload", "config2", "--steps", "2", "--warmup", "1", "--full", "FORCE_DIST"],  # the N > 1 code path (RCCL group + the sharded-plot extra) on one GPU
 ])
 def test_bench_prints_one_json_line_last(flags):
     """Every workload of bench.py end to end in a child process: exit code 0 and the LAST line of stdout is the JSON line with the
@@ -737,7 +737,7 @@ def test_bench_two_ranks_flow_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", TL_BENCH_SHARE_GPU="1", TL_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", _free_port(),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--no-fp32-mode", "--no-power-probe"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-fp32-mode", "--no-power-probe"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -753,3 +753,33 @@ def test_bench_two_ranks_flow_on_one_gpu():
     assert r2.returncode == 0, r2.stdout[-1500:] + r2.stderr[-3000:]
     last = r2.stdout.strip().splitlines()[-1]
     assert json.loads(last)["n_gpus"] == 2
+
+
+@pytest.mark.parametrize("flags, names", [
+    (["--workload", "config2", "--steps", "3", "--warmup", "1"], ("backbone_feats", "semantic_prediction_logits", "offset_predictions")),
+    (["--workload", "config3", "--steps", "1", "--warmup", "1"], ("losses", "parameters")),
+    (["--workload", "config4", "--plot-tiles", "3", "--steps", "2", "--warmup", "1"], ("semantic_prediction_logits", "offset_predictions", "coords")),
+])
+def test_bench_plain_run_is_lean_and_dumps_outputs(flags, names, tmp_path):
+    """A plain bench.py run (no --full) prints the headline line and nothing the extra measurements add, and --dump-outputs writes the
+    last timed step's arrays: float32 / float64 .npy files, finite, at most 64 MB in all."""
+    import subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *flags, "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=900, env=dict(os.environ, MASTER_ADDR="127.0.0.1"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == int(flags[flags.index("--steps") + 1])
+    assert d.get("roofline") is None
+    for k in ("latency", "one_tile_at_a_time", "fp32_parity_mode", "training_step", "config4", "config5", "host_resident_tile_loop", "power",
+              "cpu_baseline", "sharded_plot", "rccl_world"):
+        assert d.get(k) is None, k
+    files = sorted(p.name for p in out.iterdir())
+    assert set(n + ".npy" for n in names) <= set(files), files
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64_000_000
+    for f in files:
+        a = np.load(out / f)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), f

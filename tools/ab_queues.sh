@@ -1,7 +1,7 @@
 # tiles in flight x hardware queues (same box)
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/ab5; mkdir -p $O
-Q="--no-cpu-baseline --no-fp32-mode --no-power-probe --no-extra-workloads"
+Q="--full --no-cpu-baseline --no-fp32-mode --no-power-probe --no-extra-workloads"
 for rep in 1 2; do
 for cfg in "8 2" "8 3" "8 4" "8 5" "8 6" "4 3"; do
   set -- $cfg

@@ -1,5 +1,5 @@
 # latency / throughput / training with an idle host and with every granted core kept busy by other processes
-Q="--no-cpu-baseline --no-fp32-mode --no-power-probe"
+Q="--full --no-cpu-baseline --no-fp32-mode --no-power-probe"
 run() {
   python bench.py --steps 30 --warmup 6 $Q 2>/dev/null > /tmp/o.json
   python -c "

@@ -1,7 +1,7 @@
 # same-box A/B of the forward: TL_BLK=0 | TL_BLK=1 with the unit builder's side stream forced off / on / automatic; 3 tiles in flight and 1
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-ab}; mkdir -p $O
-Q="--no-cpu-baseline --no-fp32-mode --no-power-probe --no-extra-workloads"
+Q="--full --no-cpu-baseline --no-fp32-mode --no-power-probe --no-extra-workloads"
 for rep in 1 2; do
 for cfg in "0 0" "1 0" "1 1" "1 auto"; do
   set -- $cfg
