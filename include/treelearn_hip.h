@@ -526,6 +526,30 @@ int tl_knn_vote_grid(const float* ref_sorted_xyz, const int64_t* ref_sorted_labe
                      const int64_t* cell_keys, const int64_t* cell_start, int64_t ncells, const float lo[3], float h, const int32_t dims[3],
                      const float* q_xyz, int64_t nq, int k, int64_t* out_label, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ scoring a segmentation against ground truth (csrc/tl_eval.hip)
+ * Contingency table: replaces the P x G masked loop of get_detections (tree_learn/util/eval.py:7-25) and the per-pair masks of
+ * evaluate_no_partition (:100-123).  pred, gt i64[n] (n < 2^31) -> table i64[(n_pred + 1) * (n_gt + 1)] (overwritten), row-major:
+ * row 0 = every negative pred, row p + 1 = pred p (p < n_pred); column 0 = gt == non_tree_label or gt < 0, column g + 1 = gt g
+ * (g < n_gt).  Points outside those ranges are not counted.  Exact integer counts (deterministic); every detection matrix follows
+ * from the table on the host in fp64 (tp = C, fp = row sum - C, fn = column sum - C). */
+int tl_eval_contingency(const int64_t* pred, const int64_t* gt, int64_t n, int64_t n_pred, int64_t n_gt, int64_t non_tree_label,
+                        int64_t* table, tl_stream_t stream);
+/* Radial / vertical bands of matched trees: replaces evaluate_xy_partition (eval.py:127-178) and evaluate_z_partition (:182-226).
+ *   xyz f64[n,3]; gt, pred i64[n]; gt_order i64[n] with gt_start i64[n_gt + 1]: the points of gt tree g are
+ *   gt_order[gt_start[g] .. gt_start[g+1]) in ascending point order (a stable sort); pred_order / pred_start likewise for n_pred
+ *   predictions; pairs i64[m,2] = (gt g, pred p); edges f64[n_edges] (2 <= n_edges <= 257).
+ *   Out: tp, fp, fn i64[m, n_edges - 1] -- band k holds the points whose value v satisfies v >= edges[k] && v < edges[k+1]; a point of
+ *   gt g is tp if its pred is p, fn otherwise; a point of pred p whose gt is not g is fp -- and norm f64[m,3]:
+ *   TL_EVAL_XY: (position x, position y, regularised max), v = |xy - position| / regularised max, position = mean xy of the tree points
+ *     with z <= min z + 0.30 (summed in point order, eval.py:147-151), regularised max = 5th-largest v numerator over the tree (:156-160);
+ *   TL_EVAL_Z: (min z, regularised max, 0), v = (z - min z) / (regularised max - min z), regularised max = 5th-largest z (:203-208).
+ *   All value arithmetic in fp64 in the reference's operation order, no fma contraction.  One workgroup per pair; the caller ensures every
+ *   gt tree of a pair has at least 5 points. */
+enum { TL_EVAL_XY = 0, TL_EVAL_Z = 1 };
+int tl_eval_partition(const double* xyz, const int64_t* gt, const int64_t* pred, int64_t n, const int64_t* gt_order, const int64_t* gt_start,
+                      int64_t n_gt, const int64_t* pred_order, const int64_t* pred_start, int64_t n_pred, const int64_t* pairs, int64_t m,
+                      const double* edges, int n_edges, int mode, int64_t* tp, int64_t* fp, int64_t* fn, double* norm, tl_stream_t stream);
+
 
 /* ------------------------------------------------------------------ the whole eval-mode forward behind ONE call
  * Replaces, per batch of tiles, the body of `model(batch, return_loss=False)` of the reference's tile loop

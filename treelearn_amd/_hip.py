@@ -175,7 +175,10 @@ PROTOTYPES = {
     "tl_hdbscan_mst_grid": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tl_knn_vote": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp]),
     "tl_knn_vote_grid": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _c.c_float * 3, _f32, _I3, _vp, _i64, _i32, _vp, _vp]),
+    "tl_eval_contingency": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "tl_eval_partition": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
 }
+TL_EVAL_XY, TL_EVAL_Z = 0, 1
 
 _lib = None
 
