@@ -41,11 +41,12 @@ enum {
 enum { TL_F32 = 0, TL_BF16 = 1, TL_F16 = 2 };
 
 int tl_version(void);
-/* Developer tuning knobs, process-wide ("win" / "direct" / "stream" / "streamq" / "blk" / "up" / "direct_oh": enable a conv kernel
- * family or form -- "blk" the staged-unit kernel of the block-local level, "up" the scatter form of the inverse conv, "direct_oh" the
- * gather-once form of the level-1 inverse conv; "win_rows": window rows of the window kernel; "win_min_rows" / "small_rows": row
- * thresholds; "small_mode": variant of the small-level kernel; "bf16_depth": register prefetch depth 1..4).  Not needed for correct
- * results; the parity tests use them to force every family over the same data.  They are read on the host when a launch is
+/* Developer tuning knobs, process-wide.  Kernel families and forms, 1 = on (default), 0 = off: "direct" / "stream" / "streamq" /
+ * "blk" (the staged-unit kernel of the block-local level) / "up" (the scatter form of the inverse conv) / "direct_oh" (the gather-once
+ * form of the level-1 inverse conv) / "streamq_x3" (the quad-gather kernel for fp32 rows in the bf16x3 mode; 0 or 1 only).  Row
+ * thresholds: "small_rows", "wgrad_dense_min_rows".  Variants: "small_mode" (small-level conv kernel), "wgrad_dense" / "wgrad_rows" /
+ * "wgrad_dma" (weight-gradient kernels).  Any other key returns TL_ERR_ARG.  Not needed for correct results; the parity tests use them
+ * to force every family over the same data.  They are read on the host when a launch is
  * dispatched (launches already enqueued are unaffected); do not change them while another host thread is inside the library. */
 int tl_set_tuning(const char* key, int64_t value);
 const char* tl_error_string(int code);

@@ -444,9 +444,10 @@ def test_no_ones_table_knob_with_a_blocked_geometry(monkeypatch):
 
 
 def test_blk_training_conv_with_the_batchnorm_at_staging():
-    """Training forward of a block-local level-1 layer with its BatchNorm + ReLU applied when the conv stages its rows (k_conv_blk<.., TR, PRO>;
-    autograd._staged_bn_conv): the stored tensor and the statistics partial sums equal the apply pass (tl_affine_relu) + the plain training
-    launch bit for bit, with and without a residual; the 64 -> 32 conv as two staged halves equals the two launches on the activated tensor."""
+    """Training forward of a block-local level-1 layer with its BatchNorm + ReLU applied when the conv stages its rows (k_conv_blk<.., TR, PRO>,
+    reached through ops.conv_fwd(in_scale=..., epi="stats")): the stored tensor and the statistics partial sums equal the apply pass
+    (tl_affine_relu) + the plain training launch bit for bit, with and without a residual; the 64 -> 32 conv as two staged halves equals the
+    two launches on the activated tensor."""
     from treelearn_amd import ops
     batch = _batch(14.0, [3])
     _, blk = _geoms(batch)
@@ -471,26 +472,6 @@ def test_blk_training_conv_with_the_batchnorm_at_staging():
     part = ops.conv_fwd(x0, w, r, n, in_scale=sc[:32], in_shift=sh[:32], in_relu=True)
     got = ops.conv_fwd(x1, w2, r, n, residual=part, in_scale=sc[32:], in_shift=sh[32:], in_relu=True, epi="stats")
     assert torch.equal(part, part_ref) and torch.equal(ref[0], got[0]) and torch.equal(ref[1][:ref[2]], got[1][:got[2]])
-
-
-def test_training_step_staged_batchnorm_equals_the_apply_pass(monkeypatch):
-    """A whole mixed-precision step with the level-1 BatchNorms applied at staging (opt-in, TL_BLK_TRAIN_PRO=1) against the default step with
-    the apply passes: the 32 -> 32 layers are bit-identical (test above); the 64 -> 32 decoder conv as two staged halves rounds its half sums
-    once more, which every gradient downstream of it feels at the level of one bf16 rounding -- loss within 1e-3, every gradient at cosine
-    >= 0.995 (measured: 0.9989 at worst, the level-2 stride-2 conv's weight)."""
-    from treelearn_amd import autograd
-    b = make_batch([make_tile(extent=14.0, voxel=0.1, n_trees=8, fill=0.1, seed=s) for s in (5, 6)])
-    gb = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in b.items()}
-    monkeypatch.setattr(autograd, "STAGE_TRAIN", True)
-    l1, g1, _ = _train_grads(True, gb)
-    monkeypatch.setattr(autograd, "STAGE_TRAIN", False)
-    l0, g0, _ = _train_grads(True, gb)
-    assert abs(l1 - l0) <= 1e-3 * abs(l0)
-    nmax = max(float(v.norm()) for v in g0.values())
-    for k in g0:
-        a, c = g0[k], g1[k]
-        if float(a.norm()) > 1e-3 * nmax:                   # (a Linear bias in front of a BatchNorm has a zero gradient: pure rounding noise)
-            assert float((a * c).sum() / (a.norm() * c.norm())) >= 0.995, k
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])

@@ -190,46 +190,6 @@ def _host_cores():
     return n
 
 
-@pytest.mark.parametrize("level,cin,cout", [(1, 64, 64), (1, 128, 64), (2, 96, 96), (2, 192, 96), (0, 32, 32)])
-def test_config2_window_kernel_on_real_rulebooks(tile2, level, cin, cout):
-    """The opt-in window form of the 27-tap convs (tl_conv_win: dz taps of a column from one LDS-staged row window, column-form
-    rulebook) on the real rulebooks of the full tile, against the oracle on sampled rows and against the default kernels."""
-    from treelearn_amd import _hip as _h
-    if _h.lib().tl_set_tuning(b"win", 0) != 0:
-        pytest.skip("the window conv kernel is in the developer build only (python -m treelearn_amd.build --dev)")
-    from treelearn_amd import _hip, ops
-    L = _hip.lib()
-    old = _hip.WIN_KERNEL
-    _hip.WIN_KERNEL = True                                     # geometry emits the column form on every big level
-    try:
-        g = _geometry(tile2, 0.1)
-    finally:
-        _hip.WIN_KERNEL = old
-    lv = g.levels[level]
-    assert getattr(lv.nbr, "_tl_compact", None) is not None
-    gen = torch.Generator(device="cuda"); gen.manual_seed(level * 77 + cin)
-    w = torch.randn((cout, 3, 3, 3, cin), device="cuda", generator=gen) / (cin * 27) ** 0.5
-    x = torch.randn((lv.n, cin), device="cuda", generator=gen).bfloat16()
-    res = torch.randn((lv.n, cout), device="cuda", generator=gen).bfloat16()
-    wp = ops.pack_weight(w, torch.bfloat16)
-    ref_kernel = ops.conv_fwd(x, wp, lv.nbr, lv.n, residual=res)
-    outs = []
-    try:
-        _hip.check(L.tl_set_tuning(b"win", 2), "win"); _hip.check(L.tl_set_tuning(b"win_min_rows", 0), "wmr")
-        for rows, ct in ((0, 1), (0, 0), (512, 1)):
-            _hip.check(L.tl_set_tuning(b"win_rows", rows), "win_rows"); _hip.check(L.tl_set_tuning(b"win_ct", ct), "win_ct")
-            outs.append(ops.conv_fwd(x, wp, lv.nbr, lv.n, residual=res))
-    finally:
-        for k, v in ((b"win", 1 if _hip.WIN_KERNEL else 0), (b"win_min_rows", 65536), (b"win_rows", 0), (b"win_ct", 1)):
-            _hip.check(L.tl_set_tuning(k, v), "restore")
-    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])          # column form / table form / tile size: same arithmetic
-    rows = torch.randperm(lv.n, device="cuda", generator=gen)[:4096].sort().values
-    sub = lv.nbr[:, rows].T.contiguous().cpu().numpy()
-    ref = osp.conv_table(x.float().cpu(), w.bfloat16().float().cpu(), sub).numpy() + res[rows].float().cpu().numpy()
-    assert rel_err(outs[0][rows].float().cpu().numpy(), ref) < 1.2e-2
-    assert rel_err(outs[0].float().cpu().numpy(), ref_kernel.float().cpu().numpy()) < 1.2e-2
-
-
 def test_config2_full_tile_bf16_decision_level(tile2):
     """The headline mode (bf16 activations between ~70 layers) against the exact-fp32 mode on the full tile, on what the
     pipeline consumes: share of points whose tree / non-tree argmax flips, and the offset error in metres.  Weights are the

@@ -1244,65 +1244,6 @@ def test_handwritten_known_answers_through_the_hip_path():
                 assert np.abs(got - want).max() <= tol * np.abs(want).max(), (case["name"], got, want)
 
 
-@pytest.mark.parametrize("cin,cout,n_out,kind", [(64, 64, 70001, "shifted"), (64, 64, 3000, "random"), (128, 64, 66000, "mixed"), (96, 96, 66013, "shifted"),
-                                                 (192, 96, 5000, "mixed"), (128, 128, 66100, "shifted"), (256, 128, 2100, "random"), (32, 32, 67000, "mixed"),
-                                                 (64, 32, 1025, "shifted")])
-def test_conv_window_kernel_vs_oracle(cin, cout, n_out, kind):
-    """tl_conv_win (dz taps of a column served from one LDS-staged row window) against the oracle: 'shifted' tables keep every
-    neighbour near its output row (the in-window path, as on real rulebooks), 'random' tables put every neighbour outside the
-    window (the global-memory slow path), 'mixed' interleaves both and leaves whole (row, group) blocks absent; ragged row counts,
-    residual and three output views; same result from the 4-wave / 256-row and the 8-wave / 512-row form."""
-    from treelearn_amd import _hip as _h
-    if _h.lib().tl_set_tuning(b"win", 0) != 0:
-        pytest.skip("the window conv kernel is in the developer build only (python -m treelearn_amd.build --dev)")
-    from treelearn_amd import _hip, ops
-    rng = np.random.default_rng(cin + 3 * cout + n_out)
-    d = _dev()
-    n_in = n_out + 300
-    x = _bf16_round(rng.normal(size=(n_in, cin)).astype(np.float32))
-    w = _bf16_round((rng.normal(size=(cout, 3, 3, 3, cin)) / np.sqrt(cin * 27)).astype(np.float32))
-    rows = np.arange(n_out)[:, None]
-    shifted = rows + rng.integers(-40, 160, size=(1, 27)) + rng.integers(-2, 3, size=(n_out, 27))
-    shifted = np.clip(shifted, 0, n_in - 1)
-    rnd = rng.integers(0, n_in, size=(n_out, 27))
-    if kind == "shifted":
-        table = shifted
-    elif kind == "random":
-        table = rnd
-    else:
-        table = np.where(rng.uniform(size=(n_out, 27)) < 0.03, rnd, shifted)
-        table[(np.arange(n_out) // 700) % 3 == 1, 9:18] = -1
-    table = table.astype(np.int32)
-    table[rng.uniform(size=table.shape) < 0.4] = -1
-    res = _bf16_round(rng.normal(size=(n_out, cout)).astype(np.float32))
-    s2 = rng.uniform(0.5, 1.5, cout).astype(np.float32); h2 = rng.normal(0, 0.3, cout).astype(np.float32)
-    y = osp.conv_table(torch.from_numpy(x), torch.from_numpy(w), table, n_out).numpy() + res
-    T = lambda a, dt=torch.float32: torch.from_numpy(a).to(d).to(dt)
-    wp = ops.pack_weight(T(w), torch.bfloat16)
-    tab = torch.from_numpy(np.ascontiguousarray(table.T)).to(d)
-    L = _hip.lib()
-    outs = {}
-    try:
-        _hip.check(L.tl_set_tuning(b"win", 2), "win"); _hip.check(L.tl_set_tuning(b"win_min_rows", 0), "win_min_rows")
-        for wr in (0, 512):
-            _hip.check(L.tl_set_tuning(b"win_rows", wr), "win_rows")
-            wide = torch.zeros((n_out, 2 * cout), dtype=torch.bfloat16, device=d)
-            o3 = torch.empty((n_out, cout), dtype=torch.bfloat16, device=d)
-            out = ops.conv_fwd(T(x, torch.bfloat16), wp, tab, n_out, residual=T(res, torch.bfloat16),
-                               out2=(wide[:, cout:], T(s2), T(h2), True), out3=(o3, None, None, False))
-            assert rel_err(out.float().cpu().numpy(), y) < 8e-3, (wr, rel_err(out.float().cpu().numpy(), y))
-            assert rel_err(wide[:, cout:].float().cpu().numpy(), np.maximum(y * s2 + h2, 0)) < 8e-3
-            assert torch.equal(o3, out) and float(wide[:, :cout].abs().max()) == 0.0
-            outs[wr] = out
-        assert torch.equal(outs[0], outs[512])                   # tile / window size changes where rows come from, never the arithmetic
-        _hip.check(L.tl_set_tuning(b"win", 0), "win")
-        ref = ops.conv_fwd(T(x, torch.bfloat16), wp, tab, n_out, residual=T(res, torch.bfloat16))
-        assert rel_err(outs[0].float().cpu().numpy(), ref.float().cpu().numpy()) < 8e-3
-    finally:
-        _hip.check(L.tl_set_tuning(b"win", 1 if _hip.WIN_KERNEL else 0), "win"); _hip.check(L.tl_set_tuning(b"win_min_rows", 65536), "win_min_rows")
-        _hip.check(L.tl_set_tuning(b"win_rows", 0), "win_rows")
-
-
 @pytest.mark.parametrize("n,C,relu", [(5, 32, True), (1000, 32, True), (70001, 64, True), (33333, 448, True), (4097, 96, False), (257, 224, True)])
 def test_bn_train_kernels_vs_torch(n, C, relu):
     """tl_bn_train_stats / tl_affine_relu / tl_bn_train_bwd (the training-mode BatchNorm1d + ReLU pairs of blocks.py:55-70) against

@@ -37,13 +37,11 @@ for li in range(4):
     gb = (lv.n * ci * 2 + nx.n * co * 2 + 8 * nx.n * 4) / 1e9
     variants = [("default, 2 views", {}, True), ("default, 1 view", {}, False), ("direct=0, 2 views", {"direct": 0}, True),
                 ("direct=0 streamq=0, 2 views", {"direct": 0, "streamq": 0}, True)]
-    variants.append(("one row block per wave, 2 views", {"stream_rb": 1}, True))
-    variants.append(("streamq=0, two row blocks, 2 views", {"direct": 0, "streamq": 0, "stream_rb": 2}, True))
     for name, kw, two in variants:
         tune(**kw)
         f = (lambda: ops.conv_fwd(x, w, lv.child, nx.n, out=out, out2=(out2, sc, sh, True))) if two else (lambda: ops.conv_fwd(x, w, lv.child, nx.n, out=out))
         ms = t(f)
-        tune(direct=1, streamq=1, stream_rb=0)
+        tune(direct=1, streamq=1)
         print(f"down l{li+1}->l{li+2} {ci:3d}->{co:3d} n={nx.n:8d}".ljust(28), f"{name:26s} {ms:7.3f} {gb:11.3f} {gb / ms * 1e3:6.0f}", flush=True)
     # inverse: level li+1 -> li
     x = torch.randn(nx.n, co, device="cuda").bfloat16()

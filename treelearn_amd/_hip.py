@@ -14,9 +14,6 @@ LIB_PATH = os.path.join(_HERE, "lib", "libtreelearn_hip.so")
 TL_F32, TL_BF16, TL_F16 = 0, 1, 2
 TL_OK, TL_ERR_ARG, TL_ERR_UNSUPPORTED = 0, -1, -3
 TL_EPI_NONE, TL_EPI_STATS, TL_EPI_BN_BWD = 0, 1, 2
-# opt-in, developer build only: the window form of the 27-tap bf16 convs (csrc/tl_conv_win.hip) for levels of >= 65536 voxels; measured
-# at parity with the register-gather kernels on the config-2 tile, so the release library does not carry it
-WIN_KERNEL = os.environ.get("TL_CONV_WIN") == "1"
 _c = ctypes
 _vp, _i64, _i32, _f32 = _c.c_void_p, _c.c_int64, _c.c_int32, _c.c_float
 
@@ -195,9 +192,6 @@ def lib():
         for name, (res, args) in PROTOTYPES.items():
             fn = getattr(L, name)          # AttributeError if a declared symbol is not exported
             fn.restype, fn.argtypes = res, args
-        if WIN_KERNEL and L.tl_set_tuning(b"win", 1) != 0:
-            raise RuntimeError("TL_CONV_WIN=1 needs the developer build of the library (python -m treelearn_amd.build --dev): the window conv "
-                               "kernel is not part of the release build")
         for kv in filter(None, os.environ.get("TL_TUNING", "").split(",")):          # developer: TL_TUNING="key=value,..." -> tl_set_tuning at load
             k, _, v = kv.partition("=")
             if L.tl_set_tuning(k.strip().encode(), int(v)) != 0:

@@ -367,14 +367,11 @@ __global__ void __launch_bounds__(256) k_affine_relu_v8(const void* __restrict__
 }  // namespace
 
 static int64_t g_small_rows = kSmallRows;
-static int g_dbg = 0;
-static int g_bf16_depth = 0, g_bf16_units = 0;   // 0 = kernel default
 extern int g_small_mode;                          // tl_conv_small.hip
-extern int g_head_mode;                           // tl_head.hip
 extern int g_wgrad_dense;                         // tl_wgrad_dense.hip
 extern int64_t g_wgrad_dense_min_rows;
 extern int g_wgrad_rows;                          // tl_wgrad_rows.hip
-extern int g_wgrad_dma, g_wgrad_dense_gx;         // tl_wgrad_dense.hip
+extern int g_wgrad_dma;                           // tl_wgrad_dense.hip
 static int g_stream = 1;                          // use the streamed-weights register-gather kernel where it applies
 static int g_streamq = 1;                         // ... and its quad-gather form for bf16 with Cin % 64 == 0
 static int g_streamq_x3 = 1;                      // ... and for fp32 rows in the parity-fast mode (tl_set_tuning "streamq_x3")
@@ -382,11 +379,6 @@ static int g_direct = 1;                          // use the weights-in-LDS dire
 static int g_direct_oh = 1;                       // ... and its gather-once form for the level-1 inverse conv
 static int g_blk = 1;                             // use the staged-unit kernel when the caller passes the block-local rulebook form
 static int g_up = 1;                              // use the coarse-stationary inverse conv when the caller passes the scatter form of the table
-#ifdef TL_DEV                                     // the window kernel lives in the developer build only (python -m treelearn_amd.build --dev)
-static int g_win = 0;                             // window kernel (opt-in, TL_CONV_WIN=1: measured at parity with the gather kernels): 1 = shapes with >= 64 channels, 2 = all, 0 = off
-extern int g_win_rows, g_win_ct;                  // tl_conv_win.hip
-static int64_t g_win_min_rows = 65536;            // below this a 512-row tiling leaves most CUs idle
-#endif
 
 // (tl_exec.hip: may the forward hand the level-1 inverse conv its packed table?  Developer switches can take the gather-once kernel away.)
 bool tl_conv_one_hot_direct_enabled(int64_t n_out) { return g_direct && g_direct_oh && n_out > g_small_rows; }     // (small levels: the small-level kernel serves the conv, from the [8][n] table)
@@ -395,33 +387,18 @@ extern "C" {
 
 int tl_set_tuning(const char* key, int64_t value) {
   if (!key) return TL_ERR_ARG;
-  if (!strcmp(key, "bf16_depth")) { g_bf16_depth = (int)value; return TL_OK; }
-  if (!strcmp(key, "bf16_units")) { g_bf16_units = (int)value; return TL_OK; }
   if (!strcmp(key, "direct")) { g_direct = (int)value; return TL_OK; }
   if (!strcmp(key, "blk")) { g_blk = (int)value; return TL_OK; }
   if (!strcmp(key, "up")) { g_up = (int)value; return TL_OK; }
   if (!strcmp(key, "direct_oh")) { g_direct_oh = (int)value; return TL_OK; }
-#ifdef TL_DEV
-  if (!strcmp(key, "win")) { g_win = (int)value; return TL_OK; }
-  if (!strcmp(key, "win_rows")) { g_win_rows = (int)value; return TL_OK; }
-  if (!strcmp(key, "win_ct")) { g_win_ct = (int)value; return TL_OK; }
-  if (!strcmp(key, "win_min_rows")) { g_win_min_rows = value; return TL_OK; }
-#else
-  if (!strncmp(key, "win", 3)) return TL_ERR_UNSUPPORTED;         // developer build only
-#endif
   if (!strcmp(key, "stream")) { g_stream = (int)value; return TL_OK; }
   if (!strcmp(key, "streamq")) { g_streamq = (int)value; return TL_OK; }
-  if (!strcmp(key, "streamq_x3")) { g_streamq_x3 = (int)value; return TL_OK; }
-  if (!strcmp(key, "stream_rb")) return tl_stream_set_rb((int)value);
-  if (!strcmp(key, "x3_chunks")) return tl_conv_blk_x3_set_chunks((int)value);
+  if (!strcmp(key, "streamq_x3")) { if (value != 0 && value != 1) return TL_ERR_ARG; g_streamq_x3 = (int)value; return TL_OK; }
   if (!strcmp(key, "small_rows")) { g_small_rows = value; return TL_OK; }
   if (!strcmp(key, "small_mode")) { g_small_mode = (int)value; return TL_OK; }
-  if (!strcmp(key, "head_mode")) { g_head_mode = (int)value; return TL_OK; }
-  if (!strcmp(key, "dbg")) { g_dbg = (int)value; return TL_OK; }
   if (!strcmp(key, "wgrad_dense")) { g_wgrad_dense = (int)value; return TL_OK; }
   if (!strcmp(key, "wgrad_rows")) { g_wgrad_rows = (int)value; return TL_OK; }
   if (!strcmp(key, "wgrad_dma")) { g_wgrad_dma = (int)value; return TL_OK; }
-  if (!strcmp(key, "wgrad_dense_gx")) { g_wgrad_dense_gx = (int)value; return TL_OK; }
   if (!strcmp(key, "wgrad_dense_min_rows")) { g_wgrad_dense_min_rows = value; return TL_OK; }
   return TL_ERR_ARG;
 }
@@ -455,7 +432,7 @@ int tl_conv_fwd(const tl_conv_args* a, tl_stream_t stream) {
   p.out3 = a->out3; p.out3_ld = a->out3_ld; p.out3_scale = a->out3_scale; p.out3_shift = a->out3_shift; p.out3_relu = a->out3_relu;
   if ((a->out2_scale == nullptr) != (a->out2_shift == nullptr) || (a->out3_scale == nullptr) != (a->out3_shift == nullptr)) return TL_ERR_ARG;
   p.nblk = (int)tl_cdiv(a->n_out, TM);
-  p.dbg = g_dbg; p.one_hot = a->table != nullptr ? a->table_one_hot : 0;
+  p.one_hot = a->table != nullptr ? a->table_one_hot : 0;
   p.blk_unit = has_blk ? a->blk_unit : nullptr; p.blk_counter = a->blk_counter; p.blk_halo = a->blk_halo; p.blk_lrb = a->blk_lrb;
   p.blk_pmask = a->K == 27 ? a->blk_pmask : nullptr;
   p.epi_mode = a->epi_mode; p.red_part = a->red_part; p.red_nparts = a->red_nparts; p.bn_x = a->bn_x; p.bn_x_ld = a->bn_x_ld;
@@ -535,7 +512,7 @@ int tl_conv_fwd(const tl_conv_args* a, tl_stream_t stream) {
       (!a->out_scale || (((uintptr_t)a->out_scale) % 16 == 0 && ((uintptr_t)a->out_shift) % 16 == 0))) {
     if (g_direct) { const int rc = L_direct(p, TL_F32, s); if (rc != TL_ERR_UNSUPPORTED) return rc; }
     if (g_stream && g_streamq && g_streamq_x3 && p.w_x3 && !train && a->n_out > g_small_rows) {     // bf16x3: quad-coalesced gathers where the shape has an instantiation
-      const int rc = tl_launch_conv_streamq_x3(p, g_streamq_x3, s);
+      const int rc = tl_launch_conv_streamq_x3(p, s);
       if (rc != TL_ERR_UNSUPPORTED) return rc;
     }
     if (g_stream) { const int rc = L_stream(p, TL_F32, s); if (rc != TL_ERR_UNSUPPORTED) return rc; }
@@ -568,12 +545,6 @@ int tl_conv_fwd(const tl_conv_args* a, tl_stream_t stream) {
       const int rc = L_stream(p, TL_BF16, s);
       if (rc != TL_ERR_UNSUPPORTED) return rc;
     }
-#ifdef TL_DEV
-    if (!train && g_win && a->K == 27 && a->n_out >= g_win_min_rows && ((a->Cin >= 64 && a->Cout >= 64) || g_win >= 2)) {
-      const int rc = tl_launch_conv_win(p, s);
-      if (rc != TL_ERR_UNSUPPORTED) return rc;
-    }
-#endif
     if (g_direct) {
       const int rc = L_direct(p, TL_BF16, s);
       if (rc != TL_ERR_UNSUPPORTED) return rc;
@@ -587,7 +558,7 @@ int tl_conv_fwd(const tl_conv_args* a, tl_stream_t stream) {
       if (rc != TL_ERR_UNSUPPORTED) return rc;
     }
     if (train) return TL_ERR_UNSUPPORTED;
-    return f16 ? tl_launch_conv_bf16_f16(p, g_bf16_depth, g_bf16_units, s) : tl_launch_conv_bf16(p, g_bf16_depth, g_bf16_units, s);
+    return f16 ? tl_launch_conv_bf16_f16(p, s) : tl_launch_conv_bf16(p, s);
   }
   if (train || f16) return TL_ERR_UNSUPPORTED;             // scalar fallbacks: TL_F32 / TL_BF16 only
   {                                                              // 1x1 with <= 8 output channels (the heads' output Linears in training)

@@ -22,9 +22,7 @@ namespace {
 
 constexpr int TM = 128;
 
-// ABL (developer ablation, compile-time so the schedule is not perturbed): 0 = product kernel,
-// 1 = no global loads in the main loop (skeleton: LDS staging + barriers + MFMA), 2 = loads only (no LDS, no MFMA)
-template <int NB, int U, int D, bool BUF, int ABL = 0>
+template <int NB, int U, int D, bool BUF>
 __global__ void __launch_bounds__(256) k_conv_bf16(ConvP p) {
   constexpr int KCB = 32 * U;
   constexpr int PITCH = KCB * 2 + 16;              // bytes
@@ -103,17 +101,6 @@ __global__ void __launch_bounds__(256) k_conv_bf16(ConvP p) {
     const int tap = taps_s[tapo];
     chv = ch;
     unsigned m = 0;
-    if constexpr (ABL == 1) {
-#pragma unroll
-      for (int i = 0; i < APASS; ++i) a[i] = u32x4{0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int i = 0; i < BPASS; ++i) b[i] = u32x4{0u, 0u, 0u, 0u};
-      vm = 0;
-      it_ch += U;
-#pragma unroll
-      for (int r = 0; r < U; ++r) { const bool w = it_ch >= upc; it_ch -= w ? upc : 0; it_tap += w ? 1 : 0; }
-      return;
-    }
     if constexpr (use_buf) {
       // buffer loads: an absent neighbour (idx = -1) wraps to an offset beyond num_records and the hardware
       // bounds check returns zeros -- no clamp, no 64-bit address arithmetic, no masking while staging.
@@ -215,26 +202,16 @@ __global__ void __launch_bounds__(256) k_conv_bf16(ConvP p) {
 #pragma unroll
   for (int d = 0; d < D; ++d) issue(ra[d], rb[d], vmask[d], chs[d]);
   int buf = 0, s = 0;
-  u32x4 sinkv = {0u, 0u, 0u, 0u};
   for (; s + D <= nsteps; s += D) {
 #pragma unroll
     for (int d = 0; d < D; ++d) {
-      if constexpr (ABL == 2) {
-#pragma unroll
-        for (int i = 0; i < APASS; ++i) sinkv ^= ra[d][i];
-#pragma unroll
-        for (int i = 0; i < BPASS; ++i) sinkv ^= rb[d][i];
-        issue(ra[d], rb[d], vmask[d], chs[d]);
-      } else {
-        stage(buf, ra[d], rb[d], vmask[d], chs[d]);
-        __syncthreads();
-        issue(ra[d], rb[d], vmask[d], chs[d]);
-        compute(buf);
-        buf ^= 1;
-      }
+      stage(buf, ra[d], rb[d], vmask[d], chs[d]);
+      __syncthreads();
+      issue(ra[d], rb[d], vmask[d], chs[d]);
+      compute(buf);
+      buf ^= 1;
     }
   }
-  if constexpr (ABL == 2) { if ((sinkv[0] ^ sinkv[1] ^ sinkv[2] ^ sinkv[3]) == 0x12345u) acc[0][0] = 1.f; }
   const int rem = nsteps - s;                                // < D steps left, already in flight
 #pragma unroll
   for (int d = 0; d < D - 1; ++d) {
@@ -286,17 +263,8 @@ int launch_b(const ConvP& p, hipStream_t s) {
   return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
 }
 
-int g_abl = 0;
 template <int NB, int U, int D>
 int launch(const ConvP& p, hipStream_t s) {
-  if (g_abl && NB == 2 && U == 2 && D == 2) {                // ablation variants exist for the C=64 shape only
-    constexpr int PITCH = 32 * U * 2 + 16;
-    const size_t main_b = 2 * (size_t)TM * PITCH + 2 * (size_t)NB * 32 * PITCH, epi_b = 4 * (size_t)32 * (NB * 32 + 4) * 4;
-    const size_t lds = (size_t)p.K * TM * 4 + 128 + (size_t)p.Cin * 8 + (main_b > epi_b ? main_b : epi_b);
-    if (g_abl == 1) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_bf16<2, 2, 2, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); k_conv_bf16<2, 2, 2, true, 1><<<p.nblk, 256, lds, s>>>(p); }
-    else { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_bf16<2, 2, 2, true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); k_conv_bf16<2, 2, 2, true, 2><<<p.nblk, 256, lds, s>>>(p); }
-    return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
-  }
   // buffer-resource gathers need the whole input view below 4 GB (32-bit offsets)
   const int64_t ld_b = p.in_ld * 2, in_bytes = (p.n_in - 1) * ld_b + (int64_t)p.Cin * 2;
   const bool buf = in_bytes > 0 && in_bytes + 2 * ld_b < 0xFFFFFFFFll;
@@ -307,24 +275,16 @@ int launch(const ConvP& p, hipStream_t s) {
 
 // Requirements (checked by the caller): Cin % 32 == 0, Cout % 32 == 0, Cout <= 224, 16-B aligned rows
 // (in_ld, out_ld, res_ld multiples of 8; base pointers 16-B aligned).
-int tl_launch_conv_bf16(const ConvP& p, int depth, int units, hipStream_t s) {
-  g_abl = p.dbg;
-  const int nb = p.Cout / 32;
-  const int D = depth > 0 ? depth : 2;                      // measured: 2 >= 3 (occupancy) >= 1 on the config-2 levels
-  int U = units > 0 ? units : 2;
-  if (U == 4) {                                             // 4-unit steps need 2x the LDS: fall back when they do not fit
-    const size_t pitch = 32 * 4 * 2 + 16;
-    const size_t need = (size_t)p.K * TM * 4 + 128 + (size_t)p.Cin * 8 + 2 * TM * pitch + 2 * (size_t)nb * 32 * pitch;
-    if (need > 160 * 1024) U = 2;
+// Two units per step, prefetch depth 2 (measured: depth 2 >= 3 (occupancy) >= 1 on the config-2 levels).
+int tl_launch_conv_bf16(const ConvP& p, hipStream_t s) {
+  switch (p.Cout / 32) {
+    case 1: return launch<1, 2, 2>(p, s);
+    case 2: return launch<2, 2, 2>(p, s);
+    case 3: return launch<3, 2, 2>(p, s);
+    case 4: return launch<4, 2, 2>(p, s);
+    case 5: return launch<5, 2, 2>(p, s);
+    case 6: return launch<6, 2, 2>(p, s);
+    case 7: return launch<7, 2, 2>(p, s);
   }
-#define TL_CASE(NB_)                                                                       \
-  case NB_:                                                                                \
-    if (U == 4) return launch<NB_, 4, 2>(p, s);                                            \
-    if (D >= 3 && NB_ <= 3) return launch<NB_, 2, 3>(p, s);                                \
-    return launch<NB_, 2, 2>(p, s);
-  switch (nb) {
-    TL_CASE(1) TL_CASE(2) TL_CASE(3) TL_CASE(4) TL_CASE(5) TL_CASE(6) TL_CASE(7)
-  }
-#undef TL_CASE
   return TL_ERR_UNSUPPORTED;
 }

@@ -369,8 +369,6 @@ __global__ void __launch_bounds__(W * 64) k_conv_blk_x3(ConvP p, X3P xp) {
   }
 }
 
-int g_x3_chunks = 0;          // tl_set_tuning("x3_chunks"): 0 = one chunk (default: chunking measured slower, profiles/r6_x3/x3_blk.txt)
-
 template <int W, bool RES, int NV>
 int launch_x3(const ConvP& p, const X3P& xp, hipStream_t s) {
   constexpr size_t lds = (size_t)WS_B + AFF_B + (size_t)W * STAGE_B;
@@ -395,30 +393,17 @@ int tl_launch_conv_blk_x3(const ConvP& p, hipStream_t s) {
   auto al16 = [](const void* q, int64_t ld) { return ((uintptr_t)q) % 16 == 0 && ld % 4 == 0; };
   if (!al16(p.in, p.in_ld) || !al16(p.out, p.out_ld) || (p.out2 && !al16(p.out2, p.out2_ld)) || (p.res && !al16(p.res, p.res_ld)) || ((uintptr_t)p.w_x3) % 16) return TL_ERR_UNSUPPORTED;
   // launch A: input channels 0..15 -> raw sums in `out`;  launch B: input channels 16..31, + the sums of launch A, + the residual, -> the
-  // requested views.  Optionally (tl_set_tuning "x3_chunks" > 0) the rows are served in chunks, A and B of a chunk back to back, so that B
-  // would find A's sums (128 B per row) in the memory-side cache -- measured on the config-2 level (237 MB of sums): 0.354 ms unchunked,
-  // 0.362 / 0.368 / 0.398 with 2 / 3 / 4 chunks (every launch stages its 54 KB of weights per workgroup and drains 256 workgroups): off.
+  // requested views.  Serving the rows in chunks, A and B of a chunk back to back, so that B would find A's sums (128 B per row) in the
+  // memory-side cache, measured slower on the config-2 level (237 MB of sums): 0.354 ms unchunked, 0.362 / 0.368 / 0.398 with 2 / 3 / 4
+  // chunks (every launch stages its 54 KB of weights per workgroup and drains 256 workgroups; profiles/r6_x3/x3_blk.txt).
   ConvP a = p;
   a.res = nullptr; a.res_ld = 0; a.out_scale = a.out_shift = nullptr; a.out_relu = 0; a.out2 = nullptr; a.out2_scale = a.out2_shift = nullptr; a.out2_relu = 0;
   ConvP b = p;
   b.in = static_cast<const float*>(p.in) + 16;
   if (p.in_scale) { b.in_scale = p.in_scale + 16; b.in_shift = p.in_shift + 16; }
-  int nchunks = 1;
-  if (g_x3_chunks > 0) {                                      // at least g_x3_chunks, and no chunk's sums above ~120 MB (the memory-side cache holds 256 MB)
-    const int64_t by_size = (p.n_out * 128 + (120ll << 20) - 1) / (120ll << 20);
-    nchunks = (int)(by_size > g_x3_chunks ? by_size : g_x3_chunks);
-    if (nchunks > 32) nchunks = 32;
-    while (nchunks > 1 && p.n_out / nchunks < 400000) --nchunks;
-  }
-  for (int c = 0; c < nchunks; ++c) {
-    int rc = launch_x3<8, false, 1>(a, X3P{0, 0, c, nchunks}, s);
-    if (rc != TL_OK) return rc;
-    const X3P xb{1, 1, c, nchunks};
-    if (p.res) rc = p.out2 ? launch_x3<8, true, 2>(b, xb, s) : launch_x3<8, true, 1>(b, xb, s);
-    else rc = p.out2 ? launch_x3<8, false, 2>(b, xb, s) : launch_x3<8, false, 1>(b, xb, s);
-    if (rc != TL_OK) return rc;
-  }
-  return TL_OK;
+  const int rc = launch_x3<8, false, 1>(a, X3P{0, 0, 0, 1}, s);
+  if (rc != TL_OK) return rc;
+  const X3P xb{1, 1, 0, 1};
+  if (p.res) return p.out2 ? launch_x3<8, true, 2>(b, xb, s) : launch_x3<8, true, 1>(b, xb, s);
+  return p.out2 ? launch_x3<8, false, 2>(b, xb, s) : launch_x3<8, false, 1>(b, xb, s);
 }
-
-int tl_conv_blk_x3_set_chunks(int n) { g_x3_chunks = n; return TL_OK; }

@@ -1,7 +1,7 @@
 // Sparse conv, "direct" form: for layers whose whole weight tensor fits in LDS (K*Cout*Cin*sizeof <= ~110 KB:
 // every level-1 conv of the U-Net, the level-1/2 down/up convs and 1x1s).  bf16 and fp32.
 //
-// Measured on MI355X (tools/dev_gather.py): MFMA-fragment-shaped buffer gathers (32 rows x 32 B per instruction)
+// Measured on MI355X (tools/dev_gather.py, since removed): MFMA-fragment-shaped buffer gathers (32 rows x 32 B per instruction)
 // of 64-B rows run as fast as the 8-lanes-per-row staging pattern (all 27 taps of the level-1 rulebook in 0.13 ms),
 // while the LDS-staged tile kernel spends most of its time on LDS round trips and one barrier per step.  So here:
 //   * all K taps of the weights are staged ONCE per workgroup in LDS (XOR-swizzled rows, conflict-free
@@ -18,29 +18,15 @@
 
 namespace {
 
-// ABL: developer ablation bits (tools/dev_direct_abl.py; results are wrong on purpose): 1 no gathers, 2 no MFMA,
-// 4 no output stores, 8 no rulebook loads (identity rows)
 // CT: the rulebook comes in column form (p.ctab, 40 B per voxel; decode_ctab) instead of the 27-entry table (108 B)
-__device__ unsigned long long g_tmd[8];   // developer timing mode (ABL bit 16): cycles summed over waves per tile segment
 
 // TR: the training-mode epilogue (tl_conv_args.epi_mode) is compiled in; the inference instantiations (TR = false) carry none of it
 // OH: every output row has at most ONE valid table entry (inverse conv): that row is gathered once and routed to its tap by a per-lane
 // select (K gathers of which K - 1 fetch nothing otherwise); all K taps are still contracted, against zeros except one
 // X3 (fp32 storage only): split-bf16 contraction (tl_conv_internal.h: mma16_x3) on weights in the tl_pack_weight_x3 form
-template <bool BF16, int K, int NB, int UN, int G, int WAVES, int ABL = 0, bool CT = false, bool TR = false, bool OH = false, bool X3 = false>
+template <bool BF16, int K, int NB, int UN, int G, int WAVES, bool CT = false, bool TR = false, bool OH = false, bool X3 = false>
 __global__ void __launch_bounds__(WAVES * 64) k_conv_direct(ConvP p, int ntiles, int walk) {
   static_assert(!X3 || (!BF16 && !TR), "the split-bf16 contraction: fp32 rows, inference");
-  constexpr bool TM = (ABL & 16) != 0;
-  [[maybe_unused]] unsigned long long tm[6] = {0, 0, 0, 0, 0, 0}, tprev = 0;
-  auto tick = [&](int seg) __attribute__((always_inline)) {
-    if constexpr (TM) {
-      __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      if (seg >= 0) tm[seg] += t - tprev;
-      tprev = t;
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
   constexpr int EB = BF16 ? 2 : 4;                   // bytes per element
   constexpr int UB = 32 * EB;                        // bytes of one 32-channel unit of a row
   constexpr int NJ = UB / 32;                        // 16-B fragment pairs per unit (lane half h takes bytes j*32 + h*16)
@@ -79,17 +65,17 @@ __global__ void __launch_bounds__(WAVES * 64) k_conv_direct(ConvP p, int ntiles,
     for (int e = lane; e < 2 * COUT; e += 64) dw[e] = 0.0;
   }
 
-  // walk 1 (developer A/B): every XCD (block b runs on XCD b % 8) walks its own contiguous eighth of the tiles
+  // walk 1 (an experiment; the launcher passes 0): every XCD (block b runs on XCD b % 8) walks its own contiguous eighth of the tiles
   const int nblk = walk ? ((int)gridDim.x >> 3) : (int)gridDim.x, bidx = walk ? ((int)blockIdx.x >> 3) : (int)blockIdx.x;
   const int t8 = walk ? (((ntiles + 7) / 8 + WAVES - 1) / WAVES) * WAVES : ntiles;
   const int tbase = walk ? ((int)blockIdx.x & 7) * t8 : 0;
   // Column-form kernel: the lane's ten rulebook words of tile t+1 are requested right after the LAST gather group of tile t
   // (younger than every gather, so no gather wait ever includes them -- vmcnt retires in order) and are there when the next
-  // tile starts; taps are decoded from the words on use instead of being kept as 27 indices.  The per-segment timers (ABL 16)
+  // tile starts; taps are decoded from the words on use instead of being kept as 27 indices.  Per-segment timers (since removed)
   // had shown a wave spending 24 % of a tile waiting for its rulebook entries; measured 0.200 -> 0.195 / 0.191 -> 0.175 ms.
   // Requesting the tile's residual vectors ahead as well (23 % of a tile is the epilogue) pushed the kernel past 128 VGPRs
   // and gave nothing (0.197 / 0.179); the 27-entry table form spills with any of this and keeps the plain order.
-  constexpr bool PF = (K == 27 && CT) && (ABL & 32) == 0;
+  constexpr bool PF = K == 27 && CT;
   constexpr int NW = (K == 27 && CT) ? 10 : K;
   auto load_words = [&](int tile_, int (&w)[NW]) __attribute__((always_inline)) {
     const int64_t row = (int64_t)tile_ * 32 + fi;
@@ -97,7 +83,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_conv_direct(ConvP p, int ntiles,
 #pragma unroll
     for (int k = 0; k < NW; ++k) {
       if constexpr (K == 27 && CT) w[k] = rvalid ? p.ctab[(int64_t)k * p.n_out + row] : (k < 9 ? -1 : 0);
-      else w[k] = rvalid ? ((p.table && !(ABL & 8)) ? p.table[(int64_t)k * p.n_out + row] : (int)row) : -1;
+      else w[k] = rvalid ? (p.table ? p.table[(int64_t)k * p.n_out + row] : (int)row) : -1;
     }
   };
   // column form: tap k = 3 c + d of the lane's row from the column base w[c] and the presence bits (see decode_ctab)
@@ -112,7 +98,6 @@ __global__ void __launch_bounds__(WAVES * 64) k_conv_direct(ConvP p, int ntiles,
   for (int lt = bidx * WAVES + wv; lt < t8; lt += nblk * WAVES) {
     const int tile = tbase + lt;
     if (tile >= ntiles) break;
-    tick(-1);
     [[maybe_unused]] int idx[PF ? 1 : K];
     [[maybe_unused]] int twc[NW];                              // PF: the lane's rulebook words (requested during the previous tile); taps are decoded on use
     if constexpr (PF) {
@@ -128,7 +113,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_conv_direct(ConvP p, int ntiles,
         for (int k = 0; k < K; ++k) idx[k] = (v >= 0 && (v & 7) == k) ? (v >> 3) : -1;
       } else {
 #pragma unroll
-        for (int k = 0; k < K; ++k) idx[k] = rvalid ? ((p.table && !(ABL & 8)) ? p.table[(int64_t)k * p.n_out + row] : (int)row) : -1;
+        for (int k = 0; k < K; ++k) idx[k] = rvalid ? (p.table ? p.table[(int64_t)k * p.n_out + row] : (int)row) : -1;
       }
     }
 
@@ -151,8 +136,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_conv_direct(ConvP p, int ntiles,
           for (int c = 0; c < UN; ++c)
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
-              if constexpr (ABL & 1) dst[t][c][j] = u32x4{base, base + 1, base + 2, base + 3};
-              else dst[t][c][j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(base + c * UB + j * 32), 0, 0));
+              dst[t][c][j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(base + c * UB + j * 32), 0, 0));
         }
       }
     };
@@ -212,10 +196,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_conv_direct(ConvP p, int ntiles,
           }
       }
     } else {
-    if constexpr (TM) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-    tick(0);                                           // 0: rulebook entries (behind the previous tile's stores: vmcnt is in-order)
     issue(0, a[0]);
-    tick(1);                                           // 1: issuing the first group of gathers
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
       if (g + 1 < NG) issue(g + 1, a[(g + 1) & 1]);
@@ -225,9 +206,6 @@ __global__ void __launch_bounds__(WAVES * 64) k_conv_direct(ConvP p, int ntiles,
           load_words(lt2 < t8 ? tbase + lt2 : ntiles, twn);
         }
       }
-      tick(1);
-      if constexpr (TM) { if (g + 1 < NG) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G * UN * NJ) : "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-      tick(2);                                         // 2: waiting for group g
 #pragma unroll
       for (int t = 0; t < G; ++t) {
         const int k = g * G + t;
@@ -255,13 +233,11 @@ __global__ void __launch_bounds__(WAVES * 64) k_conv_direct(ConvP p, int ntiles,
 #pragma unroll
               for (int nb = 0; nb < NB; ++nb) {
                 const u32x4 bf = *reinterpret_cast<const u32x4*>(wl + ((k * UN + c) * COUT + nb * 32) * UB + (((2 * j + fh) ^ swz) * 16));
-                if constexpr (ABL & 2) acc[nb][(k + j) & 15] += __uint_as_float(a[g & 1][t][c][j][0] ^ bf[1]);
-                else mma16<BF16>(acc[nb], a[g & 1][t][c][j], bf);
+                mma16<BF16>(acc[nb], a[g & 1][t][c][j], bf);
               }
             }
         }
       }
-      tick(3);                                         // 3: LDS weight fragments + MFMAs
     }
     }
 
@@ -279,8 +255,7 @@ __global__ void __launch_bounds__(WAVES * 64) k_conv_direct(ConvP p, int ntiles,
       if (orow >= p.n_out) continue;
       const f32x4 v0 = *reinterpret_cast<const f32x4*>(ew + rr * EP + cvv * 8), v1 = *reinterpret_cast<const f32x4*>(ew + rr * EP + cvv * 8 + 4);
       float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-      if constexpr (ABL & 4) { if (v[0] == 1.2345e30f) epi_views8<BF16>(p, orow, cvv * 8, v); }
-      else epi_views8<BF16>(p, orow, cvv * 8, v);
+      epi_views8<BF16>(p, orow, cvv * 8, v);
     }
     } else {
       // training mode: the row stage writes the summands back into the tile, every lane then adds its NB columns (tl_conv_internal.h)
@@ -336,14 +311,6 @@ __global__ void __launch_bounds__(WAVES * 64) k_conv_direct(ConvP p, int ntiles,
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    tick(4);                                           // 4: epilogue (LDS transposition, residual read, stores issued)
-    if constexpr (TM) tm[5] += 1;
-  }
-  if constexpr (TM) {
-    if (lane == 0) {
-#pragma unroll
-      for (int i = 0; i < 6; ++i) atomicAdd(&g_tmd[i], tm[i]);
-    }
   }
   if constexpr (TR) {                                            // the waves' column sums, added in wave order -> the workgroup's partial row
     __syncthreads();
@@ -498,17 +465,15 @@ __global__ void __launch_bounds__(256) k_conv_ones27(ConvP p) {
   }
 }
 
-int g_direct_walk = 0;
-
-template <bool BF16, int K, int NB, int UN, int G, int WAVES, int ABL = 0, bool CT = false, bool TR = false, bool OH = false, bool X3 = false>
+template <bool BF16, int K, int NB, int UN, int G, int WAVES, bool CT = false, bool TR = false, bool OH = false, bool X3 = false>
 int launch(const ConvP& p_, hipStream_t s) {
   ConvP p = p_;
   if constexpr (X3) {
     if (p.epi_mode != TL_EPI_NONE) return TL_ERR_UNSUPPORTED;
     p.w = p.w_x3;
   }
-  if constexpr (!TR && BF16 && ABL == 0) {
-    if (p.epi_mode != TL_EPI_NONE) return launch<BF16, K, NB, UN, G, WAVES, ABL, CT, true, OH>(p, s);  // training-mode epilogue: its own instantiation
+  if constexpr (!TR && BF16) {
+    if (p.epi_mode != TL_EPI_NONE) return launch<BF16, K, NB, UN, G, WAVES, CT, true, OH>(p, s);  // training-mode epilogue: its own instantiation
   } else if constexpr (!TR) {
     if (p.epi_mode != TL_EPI_NONE) return TL_ERR_UNSUPPORTED;
   }
@@ -518,55 +483,32 @@ int launch(const ConvP& p_, hipStream_t s) {
   const size_t lds = (size_t)K * UN * NB * 32 * UB + (size_t)WAVES * 32 * (NB * 32 + 4) * 4 + (TR ? (size_t)WAVES * 2 * NB * 32 * 8 : 0);
   if (lds > 160 * 1024) return TL_ERR_UNSUPPORTED;
   static TlAttrOnce attr_once;                     // per kernel instantiation AND device (the attribute is per device)
-  if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_direct<BF16, K, NB, UN, G, WAVES, ABL, CT, TR, OH, X3>), 160 * 1024)) return TL_ERR_LAUNCH;
+  if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_direct<BF16, K, NB, UN, G, WAVES, CT, TR, OH, X3>), 160 * 1024)) return TL_ERR_LAUNCH;
   const int ntiles = (int)tl_cdiv(p.n_out, 32);
   const int per_cu = (int)((160 * 1024) / lds) < 1 ? 1 : (int)((160 * 1024) / lds);
   int grid = 256 * (per_cu > 2 ? 2 : per_cu);
   const int need = (int)tl_cdiv(ntiles, WAVES);
   if (grid > need) grid = need;
-  k_conv_direct<BF16, K, NB, UN, G, WAVES, ABL, CT, TR, OH, X3><<<grid, WAVES * 64, lds, s>>>(p, ntiles, (g_direct_walk && grid % 8 == 0) ? 1 : 0);
+  k_conv_direct<BF16, K, NB, UN, G, WAVES, CT, TR, OH, X3><<<grid, WAVES * 64, lds, s>>>(p, ntiles, 0);
   if (p.red_nparts) *p.red_nparts = grid;
   return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
   }
 }
 
-int g_direct_abl = 0;
-
 template <bool BF16, int K, int G>
 int dispatch(const ConvP& p, hipStream_t s) {
   const int nb = p.Cout / 32, un = p.Cin / 32;
-#ifdef TL_DEV
-  if constexpr (BF16 && K == 27) {
-    if (g_direct_abl && g_direct_abl < 14 && nb == 1 && un == 1) {
-      switch (g_direct_abl) {
-        case 1: return launch<true, 27, 1, 1, 3, 16, 1>(p, s);
-        case 2: return launch<true, 27, 1, 1, 3, 16, 2>(p, s);
-        case 3: return launch<true, 27, 1, 1, 3, 16, 4>(p, s);
-        case 4: return launch<true, 27, 1, 1, 3, 16, 8>(p, s);
-        case 5: return launch<true, 27, 1, 1, 3, 16, 9>(p, s);
-        case 6: return launch<true, 27, 1, 1, 3, 16, 5>(p, s);
-        case 7: return launch<true, 27, 1, 1, 3, 8>(p, s);
-        case 8: return launch<true, 27, 1, 1, 9, 16>(p, s);
-        case 9: return launch<true, 27, 1, 1, 1, 16>(p, s);
-        case 10: return launch<true, 27, 1, 1, 3, 16, 16>(p, s);     // segment timers
-      }
-    }
-  }
-#endif
   const size_t wbytes = (size_t)K * p.Cout * p.Cin * (BF16 ? 2 : 4);
   if constexpr (BF16 && K == 27) {
     // column-form rulebook (level 1), its words requested one tile ahead: 32 -> 32 0.200 -> 0.195 ms on top of the 0.243 -> 0.226 of
     // the 40-B form itself; 64 -> 32 0.51 -> 0.33 ms (without the look-ahead the decode in front of its gathers had made it slower)
-    if (p.ctab && (g_direct_abl == 0 || g_direct_abl >= 14) && nb == 1 && un == 1) return launch<true, 27, 1, 1, G, 16, 0, true>(p, s);
-    if (p.ctab && g_direct_abl != 14 && nb == 1 && un == 2) return launch<true, 27, 1, 2, G, 8, 0, true>(p, s);
-#ifdef TL_DEV
-    if (p.ctab && g_direct_abl == 13 && nb == 1 && un == 1) return launch<true, 27, 1, 1, G, 16, 32, true>(p, s);   // rulebook words not requested ahead
-#endif
+    if (p.ctab && nb == 1 && un == 1) return launch<true, 27, 1, 1, G, 16, true>(p, s);
+    if (p.ctab && nb == 1 && un == 2) return launch<true, 27, 1, 2, G, 8, true>(p, s);
   }
   if constexpr (BF16 && K == 8) {
     // inverse conv of level 1 (64 -> 32, one valid entry per row): the row gathered once, no per-tap barrier (the stream kernel's one-hot
     // form took 0.171 ms for 0.38 GB of traffic: eight barrier steps per 256 rows)
-    if (p.one_hot && nb == 1 && un == 2) return launch<true, 8, 1, 2, G, 16, 0, false, false, true>(p, s);
+    if (p.one_hot && nb == 1 && un == 2) return launch<true, 8, 1, 2, G, 16, false, false, true>(p, s);
   }
   if constexpr (BF16 && K == 1) {
     // the 1x1 convs of the decoder blocks (2C -> C on the skip concat) of levels 2-4: pure streaming, weights resident (level 2: 0.108 ms
@@ -579,13 +521,13 @@ int dispatch(const ConvP& p, hipStream_t s) {
     // the 2C -> C 1x1 conv of the level-2 decoder block on fp32 rows (exact or split-bf16): pure streaming with resident weights, as in bf16
     // (the stream kernel moved its 0.86 GB at 2.3 TB/s)
     if (nb == 2 && un == 4 && p.epi_mode == TL_EPI_NONE) {
-      if (p.w_x3) return launch<false, 1, 2, 4, 1, 8, 0, false, false, false, true>(p, s);
+      if (p.w_x3) return launch<false, 1, 2, 4, 1, 8, false, false, false, true>(p, s);
       return launch<false, 1, 2, 4, 1, 8>(p, s);
     }
   }
   if constexpr (!BF16 && K == 8) {
     // ... and the same conv in the parity-fast mode (fp32 rows, split-bf16 weights: 64 KB resident + twelve epilogue buffers)
-    if (p.one_hot && p.w_x3 && p.epi_mode == TL_EPI_NONE && nb == 1 && un == 2) return launch<false, 8, 1, 2, G, 12, 0, false, false, true, true>(p, s);
+    if (p.one_hot && p.w_x3 && p.epi_mode == TL_EPI_NONE && nb == 1 && un == 2) return launch<false, 8, 1, 2, G, 12, false, false, true, true>(p, s);
   }
   // 16-wave workgroups (bf16 only: 128 VGPRs suffice) when the weights leave room for 16 epilogue buffers
 #define TL_D(NB_, UN_)                                                                                               \
@@ -593,7 +535,7 @@ int dispatch(const ConvP& p, hipStream_t s) {
     if constexpr (BF16) return wbytes <= 64 * 1024 ? launch<true, K, NB_, UN_, G, 16>(p, s) : launch<true, K, NB_, UN_, G, 8>(p, s); \
     else {                                                                                                           \
       if (p.w_x3 && p.epi_mode == TL_EPI_NONE)       /* split-bf16: latency-bound, so as many waves as the LDS holds beside 110 KB of weights */ \
-        return launch<false, K, NB_, UN_, (G > 2 ? 2 : G), (K == 27 && NB_ == 1 && UN_ == 1 ? 11 : 8), 0, false, false, false, true>(p, s);         \
+        return launch<false, K, NB_, UN_, (G > 2 ? 2 : G), (K == 27 && NB_ == 1 && UN_ == 1 ? 11 : 8), false, false, false, true>(p, s);         \
       return launch<false, K, NB_, UN_, (G > 2 ? 2 : G), 8>(p, s);                                                   \
     }                                                                                                                \
   }
@@ -613,16 +555,6 @@ int tl_launch_conv_ones27(const ConvP& p, int dtype, hipStream_t s) {
 }
 
 
-#ifdef TL_DEV
-// developer hook (dev build only), not part of the C ABI: mode 0..99 = ablation variant of the 32->32 kernel, 1000 / 1001 = tile walk of every direct launch
-extern "C" int tl_dev_direct_abl(int mode) { if (mode >= 1000) g_direct_walk = mode - 1000; else g_direct_abl = mode; return TL_OK; }
-extern "C" int tl_dev_direct_tm(unsigned long long* out8) {          // read and clear the segment timers of ablation mode 10
-  if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_tmd), sizeof(g_tmd)) != hipSuccess) return TL_ERR_LAUNCH;
-  unsigned long long z[8] = {0};
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_tmd), z, sizeof(z)) == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
-}
-#endif
-
 // Eligibility (beyond the tile kernel's alignment rules): no gather-side prologue, whole weight tensor + epilogue
 // scratch within LDS, input view below 4 GB.  Returns TL_ERR_UNSUPPORTED when the shape is not covered.
 int tl_launch_conv_direct(const ConvP& p, int dtype, hipStream_t s) {
@@ -636,7 +568,7 @@ int tl_launch_conv_direct(const ConvP& p, int dtype, hipStream_t s) {
     if (p.epi_mode != TL_EPI_NONE) {
       if (p.ctab && p.K == 27) k_conv_in4<8, true, true><<<grid, 512, 0, s>>>(p, ntiles);
       else k_conv_in4<8, false, true><<<grid, 512, 0, s>>>(p, ntiles);
-    } else if (p.ctab && p.K == 27 && g_direct_abl != 15) k_conv_in4<8, true><<<grid, 512, 0, s>>>(p, ntiles);
+    } else if (p.ctab && p.K == 27) k_conv_in4<8, true><<<grid, 512, 0, s>>>(p, ntiles);
     else k_conv_in4<8><<<grid, 512, 0, s>>>(p, ntiles);
     if (p.red_nparts) *p.red_nparts = grid;
     return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;

@@ -8,7 +8,6 @@
 #define tl_launch_conv_direct tl_launch_conv_direct_f16
 #define tl_launch_conv_ones27 tl_launch_conv_ones27_f16
 #define tl_launch_conv_stream tl_launch_conv_stream_f16
-#define tl_stream_set_rb tl_stream_set_rb_f16
 #define tl_launch_conv_streamq tl_launch_conv_streamq_f16
 #define tl_launch_conv_small tl_launch_conv_small_f16
 #define tl_launch_conv_tinycin tl_launch_conv_tinycin_f16
@@ -51,7 +50,6 @@ struct ConvP {
   int one_hot; // every output row has at most one valid table entry (inverse conv)
   // block-local form of a 27-tap rulebook (tl_blk_build; tl_conv_args.blk_*), nullptr if absent
   const int32_t* blk_unit; const int32_t* blk_counter; const int32_t* blk_halo; const uint32_t* blk_lrb; const int32_t* blk_pmask;
-  int dbg;     // developer ablation bits (tl_set_tuning "dbg"): 1 no A loads, 2 no B loads, 4 no MFMA, 8 no stores
 };
 
 static __device__ __forceinline__ float ld_elem(const float* p) { return *p; }
@@ -329,7 +327,7 @@ static __device__ __forceinline__ void decode_ctab(const int32_t* __restrict__ c
 }
 
 // tl_conv_bf16.hip
-int tl_launch_conv_bf16(const ConvP& p, int depth, int units, hipStream_t s);   // large levels, bf16 MFMA
+int tl_launch_conv_bf16(const ConvP& p, hipStream_t s);   // large levels, bf16 MFMA
 
 // tl_conv_direct.hip
 int tl_launch_conv_direct(const ConvP& p, int dtype, hipStream_t s);   // whole weight tensor resident in LDS, per-wave tiles
@@ -342,20 +340,14 @@ int tl_launch_conv_up(const ConvP& p, const int32_t* child, hipStream_t s);   //
 int tl_launch_conv_blk(const ConvP& p, hipStream_t s);                  // 16-bit, 27 taps, 32 -> 32: rows in block-local order, staged units
 #ifndef TL_F16_BUILD
 int tl_launch_conv_blk_x3(const ConvP& p, hipStream_t s);               // fp32 rows, split-bf16 contraction (bf16x3), 27 taps, 32 -> 32: staged units, two 16-channel launches
-int tl_conv_blk_x3_set_chunks(int n);
-int tl_launch_conv_streamq_x3(const ConvP& p, int mode, hipStream_t s);          // fp32 rows, split-bf16 contraction: quad-coalesced gathers (levels 2-3)
+int tl_launch_conv_streamq_x3(const ConvP& p, hipStream_t s);                   // fp32 rows, split-bf16 contraction: quad-coalesced gathers (levels 2-3)
 #endif
 
 // tl_conv_stream.hip
 int tl_launch_conv_stream(const ConvP& p, int dtype, hipStream_t s);   // per-wave register gathers, weights streamed through LDS per tap
 
-int tl_stream_set_rb(int rb);
-
 // tl_conv_streamq.hip
 int tl_launch_conv_streamq(const ConvP& p, hipStream_t s);              // bf16, Cin % 64 == 0: quad-coalesced gathers + register transposition
-
-// tl_conv_win.hip
-int tl_launch_conv_win(const ConvP& p, hipStream_t s);                  // bf16, 27 taps: dz taps of a column share one LDS-staged row window
 
 // tl_conv_small.hip
 int tl_launch_conv_small(const ConvP& p, int dtype, hipStream_t s);     // few output rows: split the tap loop over waves
@@ -369,7 +361,7 @@ int tl_launch_conv_stream_f16(const ConvP& p, int dtype, hipStream_t s);
 int tl_launch_conv_streamq_f16(const ConvP& p, hipStream_t s);
 int tl_launch_conv_small_f16(const ConvP& p, int dtype, hipStream_t s);
 int tl_launch_conv_tinycin_f16(const ConvP& p, int dtype, hipStream_t s);
-int tl_launch_conv_bf16_f16(const ConvP& p, int depth, int units, hipStream_t s);
+int tl_launch_conv_bf16_f16(const ConvP& p, hipStream_t s);
 int tl_launch_conv_blk_f16(const ConvP& p, hipStream_t s);
 int tl_launch_conv_up_f16(const ConvP& p, const int32_t* child, hipStream_t s);
 #endif

@@ -20,12 +20,10 @@ namespace {
 constexpr int WAVES = 8;
 constexpr int NT = WAVES * 64;
 
-__device__ unsigned long long g_tm[8];   // developer timing mode (tl_dev_stream_tm): cycles summed over waves per step segment
-
 // OH (inverse conv, one valid table entry per output row): the row's single input row is gathered ONCE and routed to its
 // tap by a per-lane select, instead of K gathers of which K - 1 are out of range.
 // X3 (fp32 storage only): the contraction runs as split-bf16 products (tl_conv_internal.h: mma16_x3) on weights in the tl_pack_weight_x3 form
-template <bool BF16, int K, int NB, int UN, int DA, int RB, int OCC, bool TM = false, bool OH = false, bool X3 = false>
+template <bool BF16, int K, int NB, int UN, int DA, int RB, int OCC, bool OH = false, bool X3 = false>
 __global__ void __launch_bounds__(NT, OCC) k_conv_stream(ConvP p) {
   static_assert(!X3 || !BF16, "the split-bf16 contraction reads fp32 rows");
   constexpr int EB = BF16 ? 2 : 4, UB = 32 * EB, NJ = UB / 32, SLOTS = UB / 16;
@@ -135,24 +133,11 @@ __global__ void __launch_bounds__(NT, OCC) k_conv_stream(ConvP p) {
   store_b(0, bw0);
   __syncthreads();
 
-  [[maybe_unused]] unsigned long long tm[4] = {0, 0, 0, 0}, tprev = 0;
-  auto tick = [&](int seg) __attribute__((always_inline)) {
-    if constexpr (TM) {
-      __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      if (seg >= 0) tm[seg] += t - tprev;
-      tprev = t;
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  tick(-1);
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     if (k + 1 < K) store_b((k + 1) & 1, bw[(k + 1) % RW]);     // tap k+1's weights -> the buffer step k-1 was reading
     if (k + WA < K) load_b(k + WA, bw[(k + WA) % RW]);          // the slot just emptied
     __builtin_amdgcn_sched_barrier(0);                         // keep the request up here (hipcc sinks it below the MFMAs)
-    if constexpr (TM) { if (k + DA < K) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DA - 1) * (RB * UN * NJ + BPT) + BPT)); else asm volatile("s_waitcnt vmcnt(0)"); }
-    tick(0);
     const char* bl = Bs + (k & 1) * COUT * BROW + fi * BROW;
     if constexpr (X3) {
 #pragma unroll
@@ -207,18 +192,8 @@ __global__ void __launch_bounds__(NT, OCC) k_conv_stream(ConvP p) {
           }
         }
       }
-    tick(1);
     if constexpr (!OH) { if (k + DA < K) issue_a(k + DA, a[k % DA]); }
-    tick(2);
     if (k + 1 < K) __syncthreads();
-    tick(3);
-  }
-  if constexpr (TM) {
-    if (lane == 0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) atomicAdd(&g_tm[i], tm[i]);
-      atomicAdd(&g_tm[4], 1ull);
-    }
   }
 
   // epilogue, one 32x32 block at a time through a wave-private LDS transposition buffer (aliases the weight tiles)
@@ -242,7 +217,7 @@ __global__ void __launch_bounds__(NT, OCC) k_conv_stream(ConvP p) {
   if (p.epi_mode != TL_EPI_NONE) epi_finish_wg<WAVES, EP, NB>(p, Es, tid, red0, red1);
 }
 
-template <bool BF16, int K, int NB, int UN, int DA, int RB, bool TM = false, bool OH = false, bool X3 = false>
+template <bool BF16, int K, int NB, int UN, int DA, int RB, bool OH = false, bool X3 = false>
 int launch(ConvP p, hipStream_t s) {
   if constexpr (X3) p.w = p.w_x3;
   constexpr int EB = BF16 ? 2 : 4;
@@ -254,82 +229,53 @@ int launch(ConvP p, hipStream_t s) {
   const size_t lds = wt > ep ? wt : ep;
   if (lds > 160 * 1024) return TL_ERR_UNSUPPORTED;
   static TlAttrOnce attr_once;                     // per kernel instantiation AND device (the attribute is per device)
-  if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_stream<BF16, K, NB, UN, DA, RB, OCC, TM, OH, X3>), 160 * 1024)) return TL_ERR_LAUNCH;
+  if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_stream<BF16, K, NB, UN, DA, RB, OCC, OH, X3>), 160 * 1024)) return TL_ERR_LAUNCH;
   p.nblk = (int)tl_cdiv(p.n_out, WAVES * 32 * RB);
-  k_conv_stream<BF16, K, NB, UN, DA, RB, OCC, TM, OH, X3><<<p.nblk, NT, lds, s>>>(p);
+  k_conv_stream<BF16, K, NB, UN, DA, RB, OCC, OH, X3><<<p.nblk, NT, lds, s>>>(p);
   if (p.red_nparts) *p.red_nparts = p.nblk;
   return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
 }
-
-int g_stream_da = 0;
-int g_stream_tm = 0;     // developer timing mode on the 64->64 bf16 shape
-int g_stream_rb = 0;     // bf16: 32-row blocks per wave (tl_set_tuning "stream_rb"): 1, 2, or 0 = measured best per shape (2 for 96->96)
 
 template <bool BF16, int K>
 int dispatch(const ConvP& p, hipStream_t s) {
   const int nb = p.Cout / 32, un = p.Cin / 32;
   if constexpr (BF16 && K == 8) {
     if (p.one_hot) {                                          // the up (inverse) convs of the large levels
-      if (nb == 2 && un == 3) return launch<true, 8, 2, 3, 1, 1, false, true>(p, s);
-      if (nb == 1 && un == 2) return launch<true, 8, 1, 2, 1, 1, false, true>(p, s);
-      if (nb == 3 && un == 4) return launch<true, 8, 3, 4, 1, 1, false, true>(p, s);
+      if (nb == 2 && un == 3) return launch<true, 8, 2, 3, 1, 1, true>(p, s);
+      if (nb == 1 && un == 2) return launch<true, 8, 1, 2, 1, 1, true>(p, s);
+      if (nb == 3 && un == 4) return launch<true, 8, 3, 4, 1, 1, true>(p, s);
     }
   }
   if constexpr (!BF16 && K == 8) {
     // ... and the same convs in the parity-fast mode (fp32 rows, split-bf16 weights): the one row gathered and split once instead of eight
     // gathered rows -- seven of them absent -- split per tap (level 2 <- 3: 0.37 ms for 0.39 GB)
     if (p.one_hot == 1 && p.w_x3 && p.epi_mode == TL_EPI_NONE) {
-      if (nb == 2 && un == 3) return launch<false, 8, 2, 3, 1, 1, false, true, true>(p, s);
-      if (nb == 3 && un == 4) return launch<false, 8, 3, 4, 1, 1, false, true, true>(p, s);
+      if (nb == 2 && un == 3) return launch<false, 8, 2, 3, 1, 1, true, true>(p, s);
+      if (nb == 3 && un == 4) return launch<false, 8, 3, 4, 1, 1, true, true>(p, s);
     }
   }
   if constexpr (BF16 && K == 8) {
     // the level-1 -> 2 strided conv (two output views, 1.7 of 8 taps present): two row blocks per wave -- half as many workgroups, each
     // amortising its start (table, first gathers) and drain (the stores of two views) over 512 rows: 0.162 -> 0.124 ms with two views,
     // 0.090 -> 0.086 with one; prefetch depth 4 / 6 / 8: no change; three or four row blocks: 0.128 (tools/dev_k8.py)
-    if (!p.one_hot && nb == 2 && un == 1 && g_stream_rb != 1) return launch<true, 8, 2, 1, 3, 2>(p, s);
+    if (!p.one_hot && nb == 2 && un == 1) return launch<true, 8, 2, 1, 3, 2>(p, s);
   }
-  if constexpr (BF16 && K == 27) {
-    if (g_stream_tm && nb == 2 && un == 2) return launch<true, 27, 2, 2, 3, 1, true>(p, s);
-    if (g_stream_da && nb == 2 && un == 2) {                  // developer A/B of the prefetch depth on the 64->64 shape
-      if (g_stream_da == 2) return launch<true, 27, 2, 2, 2, 1>(p, s);
-      if (g_stream_da == 4) return launch<true, 27, 2, 2, 4, 1>(p, s);
-      if (g_stream_da == 5) return launch<true, 27, 2, 2, 5, 1>(p, s);
-    }
-  }
-  // (NB, UN): bf16 with one row block per wave (prefetch depth DB1) or two (DB2, 0 = not offered); fp32: one (depth DF)
-#define TL_S(NB_, UN_, DB1_, DB2_, DF_)                                                              \
+  // (NB, UN): bf16 with RB_ 32-row blocks per wave (two measured best for 96 -> 96) at prefetch depth DB_; fp32: one row block, depth DF_
+#define TL_S(NB_, UN_, DB_, RB_, DF_)                                                                \
   if (nb == NB_ && un == UN_) {                                                                      \
-    if constexpr (BF16) {                                                                            \
-      if (DB2_ > 0 && (g_stream_rb == 2 || (g_stream_rb == 0 && NB_ == 3 && UN_ == 3))) return launch<true, K, NB_, UN_, (DB2_ > 0 ? DB2_ : 1), 2>(p, s); \
-      return launch<true, K, NB_, UN_, DB1_, 1>(p, s);                                               \
-    } else {                                                                                         \
-      if (p.w_x3) return launch<false, K, NB_, UN_, 1, 1, false, false, true>(p, s);   /* split-bf16 contraction */ \
+    if constexpr (BF16) return launch<true, K, NB_, UN_, DB_, RB_>(p, s);                            \
+    else {                                                                                           \
+      if (p.w_x3) return launch<false, K, NB_, UN_, 1, 1, false, true>(p, s);   /* split-bf16 contraction */ \
       return launch<false, K, NB_, UN_, DF_, 1>(p, s);                                               \
     }                                                                                                \
   }
-  TL_S(2, 2, 3, 2, 2) TL_S(2, 4, 2, 1, 1) TL_S(3, 3, 2, 1, 1) TL_S(3, 6, 1, 0, 1) TL_S(4, 4, 2, 0, 1) TL_S(2, 3, 3, 1, 1) TL_S(3, 2, 3, 2, 2)
-  TL_S(3, 4, 2, 1, 1) TL_S(4, 3, 2, 1, 1) TL_S(1, 2, 3, 2, 2) TL_S(2, 1, 3, 2, 2) TL_S(1, 1, 3, 2, 2)
+  TL_S(2, 2, 3, 1, 2) TL_S(2, 4, 2, 1, 1) TL_S(3, 3, 1, 2, 1) TL_S(3, 6, 1, 1, 1) TL_S(4, 4, 2, 1, 1) TL_S(2, 3, 3, 1, 1) TL_S(3, 2, 3, 1, 2)
+  TL_S(3, 4, 2, 1, 1) TL_S(4, 3, 2, 1, 1) TL_S(1, 2, 3, 1, 2) TL_S(2, 1, 3, 1, 2) TL_S(1, 1, 3, 1, 2)
 #undef TL_S
   return TL_ERR_UNSUPPORTED;
 }
 
 }  // namespace
-
-int tl_stream_set_rb(int rb) { if (rb >= 100) g_stream_da = rb - 100; else g_stream_rb = rb; return TL_OK; }
-
-// Developer hook (not part of the C ABI): switch the per-segment cycle counters on/off, read and clear them.
-#ifdef TL_DEV
-extern "C" int tl_dev_stream_tm(int enable, unsigned long long* out8) {
-  g_stream_tm = enable;
-  if (out8) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_tm), sizeof(g_tm)) != hipSuccess) return TL_ERR_LAUNCH;
-    unsigned long long z[8] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_tm), z, sizeof(z)) != hipSuccess) return TL_ERR_LAUNCH;
-  }
-  return TL_OK;
-}
-#endif
 
 int tl_launch_conv_stream(const ConvP& p, int dtype, hipStream_t s) {
   if (p.in_scale || p.in_relu) return TL_ERR_UNSUPPORTED;

@@ -2,9 +2,9 @@
 //
 // Why: a 32x32x16 MFMA wants its A operand as (lane & 31) = row, (lane >> 5) = which 16 B of the row -- loading that shape
 // straight from global memory makes every lane of a buffer_load_b128 its own 16-B request (32 rows x 2 pieces per
-// instruction).  Measured on the level-2 rulebook (tools/dev_gather.py): 27 taps of such gathers alone take 0.26 ms, while
+// instruction).  Measured on the level-2 rulebook (tools/dev_gather.py, since removed): 27 taps of such gathers alone take 0.26 ms, while
 // the same bytes fetched with four ADJACENT lanes reading 64 contiguous bytes take 0.135 ms -- the texture-address path
-// works on quads.  And tools/dev_stream_tm.py showed the stream kernel's waves stalled a quarter of their time just
+// works on quads.  And per-segment timers (since removed) showed the stream kernel's waves stalled a quarter of their time just
 // issuing the fragment-shaped loads (the request queue was full) and another third at the per-tap barrier behind them.
 //
 // So here a wave gathers its 32 rows quad-wise -- load i (0..3) of a 128-B part: lane l reads row ((l>>2)&7) + 8 i, bytes
@@ -24,8 +24,6 @@
 #include <type_traits>
 
 namespace {
-
-__device__ unsigned long long g_tmq[8];   // developer timing mode (tl_dev_streamq_tm)
 
 template <int CTRL>
 static __device__ __forceinline__ uint32_t qperm(uint32_t v) {
@@ -56,7 +54,6 @@ static __device__ __forceinline__ void quad_transpose(const u32x4 (&S)[4], u32x4
 }
 
 // W waves per workgroup, each owning RB blocks of 32 rows (one weight fragment read from LDS feeds RB MFMAs).
-// ABL: developer ablation bits (1 no transposition, 2 no gathers, 4 no barrier, 8 no MFMA, 16 timers, 32 MFMAs for taps < 16 only)
 // SP: the input channels are walked in SP slices of PN * 64: step v of the K * SP steps contracts slice v % SP of tap v / SP
 // (same registers and LDS as the PN-wide kernel; 256 -> 128 as SP = 2 x 128 instead of a PN = 4 kernel that spills).
 // X3 (round 6; fp32 rows, the parity-fast mode "bf16x3"): a 128-B part is 32 fp32 channels.  The gathers and the transposition do not care --
@@ -65,9 +62,8 @@ static __device__ __forceinline__ void quad_transpose(const u32x4 (&S)[4], u32x4
 // (channels 16 J + 4 fh + {0..3} and 16 J + 8 + 4 fh + {0..3}), whose rows [K][Cout][Cin / 32][128 B] are byte for byte the weight rows this
 // kernel streams: two k-steps per part, three MFMAs each (lo.Whi + hi.Wlo + hi.Whi), fp32 epilogue.  The split-bf16 form of tl_conv_stream.hip
 // issues one 16-B request per lane and piece (fragment shape); here four adjacent lanes read 64 contiguous bytes.
-template <int K, int NB, int PN, int DA, int W, int RB, int OCC, int ABL, int SP = 1, bool X3 = false, bool UL = false>
+template <int K, int NB, int PN, int DA, int W, int RB, int OCC, int SP = 1, bool X3 = false, bool UL = false>
 __global__ void __launch_bounds__(W * 64, OCC) k_conv_streamq(ConvP p) {
-  constexpr bool TM = (ABL & 16) != 0;
   constexpr int KV = K * SP;
   constexpr int NTH = W * 64;
   constexpr int COUT = NB * 32, CIN = PN * 64;
@@ -77,7 +73,6 @@ __global__ void __launch_bounds__(W * 64, OCC) k_conv_streamq(ConvP p) {
   constexpr int BPT = (BVEC + NTH - 1) / NTH;
   constexpr int EP = 32 + 4;
   constexpr int WB = 2 * COUT * BROW;
-  constexpr int LA = 4 * PN * RB;                     // gather instructions per tap
   constexpr int WROWS = 32 * RB;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Bs = smem;                                                          // [2][COUT][BROW]
@@ -149,8 +144,7 @@ __global__ void __launch_bounds__(W * 64, OCC) k_conv_streamq(ConvP p) {
         const unsigned base = idn[rb][i] * (unsigned)in_ld_b + qoff + (unsigned)((v % SP) * CIN * 2);
 #pragma unroll
         for (int pp = 0; pp < PN; ++pp) {
-          if constexpr (ABL & 2) dst[rb][pp][i] = u32x4{base, base, base, base};
-          else dst[rb][pp][i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(base + pp * 128), 0, 0));
+          dst[rb][pp][i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(base + pp * 128), 0, 0));
         }
       }
   };
@@ -181,17 +175,6 @@ __global__ void __launch_bounds__(W * 64, OCC) k_conv_streamq(ConvP p) {
   store_b(0, bw0);
   __syncthreads();
 
-  [[maybe_unused]] unsigned long long tm[4] = {0, 0, 0, 0}, tprev = 0;
-  auto tick = [&](int seg) __attribute__((always_inline)) {
-    if constexpr (TM) {
-      __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long t = __builtin_amdgcn_s_memtime();
-      if (seg >= 0) tm[seg] += t - tprev;
-      tprev = t;
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  tick(-1);
   // one step of the tap loop; U = k % DA (and the parity of k: DA is even) as a compile-time constant, so that the register arrays keep
   // static indices when the loop is NOT fully unrolled (the X3 bodies are three times the size of the bf16 ones: hipcc refuses to unroll
   // 27 / 54 of them and would otherwise index a[] / bw[] dynamically, i.e. through scratch memory)
@@ -200,15 +183,12 @@ __global__ void __launch_bounds__(W * 64, OCC) k_conv_streamq(ConvP p) {
     if (k + 1 < KV) store_b((U + 1) & 1, bw[(U + 1) % RW]);
     if (k + WA < KV) load_b(k + WA, bw[(U + WA) % RW]);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (TM) { if (k + DA < KV) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DA - 1) * (LA + BPT) + BPT)); else asm volatile("s_waitcnt vmcnt(0)"); }
-    tick(0);
     u32x4 F[RB][PN][4];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
       for (int pp = 0; pp < PN; ++pp) {
-        if constexpr (ABL & 1) { for (int i = 0; i < 4; ++i) F[rb][pp][i] = a[U % DA][rb][pp][i]; }
-        else quad_transpose(a[U % DA][rb][pp], F[rb][pp], o0, o1);
+        quad_transpose(a[U % DA][rb][pp], F[rb][pp], o0, o1);
       }
     const char* bl = Bs + (U & 1) * COUT * BROW + fi * BROW + fh * 64;
     if constexpr (X3) {
@@ -238,16 +218,11 @@ __global__ void __launch_bounds__(W * 64, OCC) k_conv_streamq(ConvP p) {
           const u32x4 bf = *reinterpret_cast<const u32x4*>(bl + nb * 32 * BROW + (pp * 8 + s) * 16);
 #pragma unroll
           for (int rb = 0; rb < RB; ++rb) {
-            if constexpr ((ABL & 8) != 0) acc[rb][nb][0] += __uint_as_float(F[rb][pp][s][0] ^ bf[0]);
-            else if ((ABL & 32) != 0 && k / SP >= 16) acc[rb][nb][0] += __uint_as_float(F[rb][pp][s][0] ^ bf[0]);
-            else mma16<true>(acc[rb][nb], F[rb][pp][s], bf);
+            mma16<true>(acc[rb][nb], F[rb][pp][s], bf);
           }
         }
-    tick(1);
     if (k + DA < KV) { issue_a(k + DA, a[U % DA]); if (k + DA + 1 < KV) read_idx(k + DA + 1); }
-    tick(2);
-    if constexpr ((ABL & 4) == 0) { if (k + 1 < KV) __syncthreads(); }
-    tick(3);
+    if (k + 1 < KV) __syncthreads();
   };
   if constexpr (X3 && !UL) {                        // two steps per trip: the parity of k (and with it every register-array index) stays static
     for (int k0 = 0; k0 < KV; k0 += 2) {
@@ -267,15 +242,12 @@ __global__ void __launch_bounds__(W * 64, OCC) k_conv_streamq(ConvP p) {
     if (k + 1 < KV) store_b((k + 1) & 1, bw[(k + 1) % RW]);
     if (k + WA < KV) load_b(k + WA, bw[(k + WA) % RW]);
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (TM) { if (k + DA < KV) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DA - 1) * (LA + BPT) + BPT)); else asm volatile("s_waitcnt vmcnt(0)"); }
-    tick(0);
     u32x4 F[RB][PN][4];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
       for (int pp = 0; pp < PN; ++pp) {
-        if constexpr (ABL & 1) { for (int i = 0; i < 4; ++i) F[rb][pp][i] = a[k % DA][rb][pp][i]; }
-        else quad_transpose(a[k % DA][rb][pp], F[rb][pp], o0, o1);
+        quad_transpose(a[k % DA][rb][pp], F[rb][pp], o0, o1);
       }
     const char* bl = Bs + (k & 1) * COUT * BROW + fi * BROW + fh * 64;
 #pragma unroll
@@ -287,24 +259,12 @@ __global__ void __launch_bounds__(W * 64, OCC) k_conv_streamq(ConvP p) {
           const u32x4 bf = *reinterpret_cast<const u32x4*>(bl + nb * 32 * BROW + (pp * 8 + s) * 16);
 #pragma unroll
           for (int rb = 0; rb < RB; ++rb) {
-            if constexpr ((ABL & 8) != 0) acc[rb][nb][0] += __uint_as_float(F[rb][pp][s][0] ^ bf[0]);
-            else if ((ABL & 32) != 0 && k / SP >= 16) acc[rb][nb][0] += __uint_as_float(F[rb][pp][s][0] ^ bf[0]);
-            else mma16<true>(acc[rb][nb], F[rb][pp][s], bf);
+            mma16<true>(acc[rb][nb], F[rb][pp][s], bf);
           }
         }
-    tick(1);
     if (k + DA < KV) { issue_a(k + DA, a[k % DA]); if (k + DA + 1 < KV) read_idx(k + DA + 1); }
-    tick(2);
-    if constexpr ((ABL & 4) == 0) { if (k + 1 < KV) __syncthreads(); }
-    tick(3);
+    if (k + 1 < KV) __syncthreads();
   }
-  }
-  if constexpr (TM) {
-    if (lane == 0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) atomicAdd(&g_tmq[i], tm[i]);
-      atomicAdd(&g_tmq[4], 1ull);
-    }
   }
 
   // epilogue: MFMA row m = (r & 3) + 8 (r >> 2) + 4 fh is tile row rho(m) = ((m >> 2) & 7) + 8 (m & 3) = 2 (r >> 2) + fh + 8 (r & 3)
@@ -328,7 +288,7 @@ __global__ void __launch_bounds__(W * 64, OCC) k_conv_streamq(ConvP p) {
   if (p.epi_mode != TL_EPI_NONE) epi_finish_wg<W, EP, NB>(p, Es, tid, red0, red1);
 }
 
-template <int K, int NB, int PN, int DA, int W = 8, int RB = 1, int ABL = 0, int SP = 1, bool X3 = false, bool UL = false>
+template <int K, int NB, int PN, int DA, int W = 8, int RB = 1, int SP = 1, bool X3 = false, bool UL = false>
 int launch(ConvP p, hipStream_t s) {
   constexpr int OCC = 2;
   if constexpr (X3) p.w = p.w_x3;
@@ -336,32 +296,14 @@ int launch(ConvP p, hipStream_t s) {
   const size_t lds = wt > ep ? wt : ep;
   if (lds > 160 * 1024) return TL_ERR_UNSUPPORTED;
   static TlAttrOnce attr_once;                     // per kernel instantiation AND device (the attribute is per device)
-  if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_streamq<K, NB, PN, DA, W, RB, OCC, ABL, SP, X3, UL>), 160 * 1024)) return TL_ERR_LAUNCH;
+  if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_streamq<K, NB, PN, DA, W, RB, OCC, SP, X3, UL>), 160 * 1024)) return TL_ERR_LAUNCH;
   p.nblk = (int)tl_cdiv(p.n_out, W * 32 * RB);
-  k_conv_streamq<K, NB, PN, DA, W, RB, OCC, ABL, SP, X3, UL><<<p.nblk, W * 64, lds, s>>>(p);
+  k_conv_streamq<K, NB, PN, DA, W, RB, OCC, SP, X3, UL><<<p.nblk, W * 64, lds, s>>>(p);
   if (p.red_nparts) *p.red_nparts = p.nblk;
   return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
 }
 
-#ifdef TL_DEV
-int g_tm_on = 0;
-#endif
-
 }  // namespace
-
-#ifdef TL_DEV
-// Developer hook (dev build only, `python -m treelearn_amd.build --dev`; not part of the C ABI): per-segment cycle counters of
-// the 64->64 shape on/off, read and clear.
-extern "C" int tl_dev_streamq_tm(int enable, unsigned long long* out8) {
-  g_tm_on = enable;
-  if (out8) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_tmq), sizeof(g_tmq)) != hipSuccess) return TL_ERR_LAUNCH;
-    unsigned long long z[8] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_tmq), z, sizeof(z)) != hipSuccess) return TL_ERR_LAUNCH;
-  }
-  return TL_OK;
-}
-#endif
 
 int tl_launch_conv_streamq(const ConvP& p, hipStream_t s) {
   if (p.in_scale || p.in_relu || p.Cin % 64 || p.Cout % 32) return TL_ERR_UNSUPPORTED;
@@ -369,33 +311,12 @@ int tl_launch_conv_streamq(const ConvP& p, hipStream_t s) {
   if (!(in_bytes > 0 && in_bytes + 2 * ld_b < 0xFFFFFFFFll)) return TL_ERR_UNSUPPORTED;
   const int nb = p.Cout / 32, pn = p.Cin / 64;
   if (p.K == 27) {
-#ifdef TL_DEV
-    if (g_tm_on && nb == 2 && pn == 1) {
-      switch (g_tm_on) {
-        case 1: return launch<27, 2, 1, 2, 8, 1, 16>(p, s);
-        case 2: return launch<27, 2, 1, 2, 8, 1, 1>(p, s);
-        case 3: return launch<27, 2, 1, 2, 8, 1, 2>(p, s);
-        case 4: return launch<27, 2, 1, 2, 8, 1, 4>(p, s);
-        case 6: return launch<27, 2, 1, 2, 8, 1, 3>(p, s);
-        case 8: return launch<27, 2, 1, 3, 8, 1>(p, s);
-        case 9: return launch<27, 2, 1, 1, 8, 1>(p, s);
-        case 10: return launch<27, 2, 1, 2, 4, 1>(p, s);
-        case 11: return launch<27, 2, 1, 2, 4, 2>(p, s);
-        case 12: return launch<27, 2, 1, 2, 8, 2>(p, s);
-        case 13: return launch<27, 2, 1, 1, 4, 2>(p, s);
-        case 14: return launch<27, 2, 1, 3, 4, 2>(p, s);
-        case 15: return launch<27, 2, 1, 2, 4, 2, 2>(p, s);
-        case 20: return p.table ? launch<16, 2, 1, 2>(p, s) : TL_ERR_ARG;      // the first 16 taps only: gathers AND MFMAs (tools/dev_l2_floor.py)
-        case 21: return launch<27, 2, 1, 2, 8, 1, 32>(p, s);                   // all 27 gathers, MFMAs for 16 taps
-      }
-    }
-#endif
     if (nb == 2 && pn == 1) return launch<27, 2, 1, 2>(p, s);
     if (nb == 2 && pn == 2) return launch<27, 2, 2, 2>(p, s);
     if (nb == 4 && pn == 2) return launch<27, 4, 2, 2>(p, s);
     if (nb == 4 && pn == 1) return launch<27, 4, 1, 2>(p, s);          // 64 -> 128: the dgrad of the level-2 128 -> 64 conv
     if (nb == 3 && pn == 3) return launch<27, 3, 3, 2>(p, s);
-    if (nb == 4 && pn == 4) return launch<27, 4, 2, 2, 8, 1, 0, 2>(p, s);
+    if (nb == 4 && pn == 4) return launch<27, 4, 2, 2, 8, 1, 2>(p, s);
   } else if (p.K == 8) {
     if (nb == 3 && pn == 1) return launch<8, 3, 1, 2>(p, s);
   }
@@ -404,29 +325,15 @@ int tl_launch_conv_streamq(const ConvP& p, hipStream_t s) {
 
 #ifndef TL_F16_BUILD
 // fp32 rows, split-bf16 contraction (p.w_x3 in the tl_pack_weight_x3 layout), 27 taps, Cin a multiple of 32 (one 128-B part per 32 channels)
-int tl_launch_conv_streamq_x3(const ConvP& p, int mode, hipStream_t s) {
+int tl_launch_conv_streamq_x3(const ConvP& p, hipStream_t s) {
   if (!p.w_x3 || p.in_scale || p.in_relu || p.Cin % 32 || p.Cout % 32 || p.K != 27 || p.epi_mode != TL_EPI_NONE || p.Cin >= 256) return TL_ERR_UNSUPPORTED;
   const int64_t ld_b = p.in_ld * 4, in_bytes = (p.n_in - 1) * ld_b + (int64_t)p.Cin * 4;
   if (!(in_bytes > 0 && in_bytes + 2 * ld_b < 0xFFFFFFFFll) || ((uintptr_t)p.w_x3) % 16) return TL_ERR_UNSUPPORTED;
   const int nb = p.Cout / 32, pn = p.Cin / 32;
-  // developer modes (tl_set_tuning "streamq_x3"): 0 = off, 1 = the shipped choice, 2 = prefetch depth 2 / two-step loop for every shape, 3 = depth 1 /
-  // two-step loop for every shape
-  if (mode == 2) {
-    if (nb == 2 && pn == 2) return launch<27, 2, 2, 2, 8, 1, 0, 1, true>(p, s);
-    if (nb == 2 && pn == 4) return launch<27, 2, 2, 2, 8, 1, 0, 2, true>(p, s);
-    if (nb == 3 && pn == 3) return launch<27, 3, 3, 2, 8, 1, 0, 1, true>(p, s);
-    if (nb == 3 && pn == 6) return launch<27, 3, 3, 2, 8, 1, 0, 2, true>(p, s);
-  }
-  if (mode == 3) {
-    if (nb == 2 && pn == 2) return launch<27, 2, 2, 1, 8, 1, 0, 1, true>(p, s);
-    if (nb == 2 && pn == 4) return launch<27, 2, 2, 1, 8, 1, 0, 2, true>(p, s);
-    if (nb == 3 && pn == 3) return launch<27, 3, 3, 1, 8, 1, 0, 1, true>(p, s);
-    if (nb == 3 && pn == 6) return launch<27, 3, 3, 1, 8, 1, 0, 2, true>(p, s);
-  }
   // shipped (config-2 rulebooks, profiles/r6_x3/x3_l2.txt; fragment-shape kernel -> this one): the 96 -> 96 shape gains nothing and stays there
-  if (nb == 2 && pn == 2) return launch<27, 2, 2, 1, 8, 1, 0, 1, true, true>(p, s);    // 64 -> 64  (level 2): 0.79-0.88 -> 0.74-0.82 ms (depth 1, fully unrolled: 114 registers, two workgroups per CU)
-  if (nb == 2 && pn == 4) return launch<27, 2, 2, 1, 8, 1, 0, 2, true>(p, s);          // 128 -> 64 (level 2 decoder): 1.75 -> 1.52 ms
-  if (nb == 3 && pn == 6) return launch<27, 3, 3, 2, 8, 1, 0, 2, true>(p, s);          // 192 -> 96 (level 3 decoder): 0.89 -> 0.82 ms
+  if (nb == 2 && pn == 2) return launch<27, 2, 2, 1, 8, 1, 1, true, true>(p, s);    // 64 -> 64  (level 2): 0.79-0.88 -> 0.74-0.82 ms (depth 1, fully unrolled: 114 registers, two workgroups per CU)
+  if (nb == 2 && pn == 4) return launch<27, 2, 2, 1, 8, 1, 2, true>(p, s);             // 128 -> 64 (level 2 decoder): 1.75 -> 1.52 ms
+  if (nb == 3 && pn == 6) return launch<27, 3, 3, 2, 8, 1, 2, true>(p, s);             // 192 -> 96 (level 3 decoder): 0.89 -> 0.82 ms
   return TL_ERR_UNSUPPORTED;
 }
 #endif

@@ -12,11 +12,9 @@
 #define tl_conv_wgrad_ref tl_conv_wgrad_ref_f16
 #define tl_conv_wgrad_blk tl_conv_wgrad_blk_f16
 #define tl_conv_wgrad_blk_ws_floats tl_conv_wgrad_blk_ws_floats_f16
-#define tl_dev_wgrad_mode tl_dev_wgrad_mode_f16
 #define g_wgrad_dma g_wgrad_dma_f16
 #define g_wgrad_dense g_wgrad_dense_f16
 #define g_wgrad_dense_min_rows g_wgrad_dense_min_rows_f16
-#define g_wgrad_dense_gx g_wgrad_dense_gx_f16
 #define g_wgrad_rows g_wgrad_rows_f16
 #define tl_launch_wgrad_reduce tl_launch_wgrad_reduce_f16
 #define tl_wgrad_dense_slots tl_wgrad_dense_slots_f16

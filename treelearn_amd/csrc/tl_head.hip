@@ -9,9 +9,7 @@
 
 #ifdef TL_F16_BUILD       // the float16 build of this unit (tl_half.h): tl_head_mlp_f16, reached from tl_head_mlp(dtype = TL_F16)
 #define tl_head_mlp tl_head_mlp_f16
-extern int g_head_mode;
 #else
-int g_head_mode = 0;      // developer A/B (tl_set_tuning "head_mode"): 1 = the scalar-weight kernel also for bf16 C = 32
 extern "C" int tl_head_mlp_f16(const void* feats, int64_t feats_ld, int dtype, int C, const int64_t* v2p, int64_t N, const float* pro_scale,
                                const float* pro_shift, const float* w1, const float* b1, const float* w2, const float* b2, float* backbone,
                                float* logits, float* offsets, tl_stream_t stream);
@@ -182,7 +180,7 @@ int launch_head(const void* feats, int64_t ld, int dtype, const int64_t* v2p, in
                 const float* w1, const float* b1, const float* w2, const float* b2, float* bb, float* lg, float* of, hipStream_t s) {
   const unsigned g = tl_grid(N, 256);
   if constexpr (C == 32) {
-    if (dtype == TL_BF16 && g_head_mode != 1) {
+    if (dtype == TL_BF16) {
       const int64_t need = tl_cdiv(tl_cdiv(N, 32), 4);
       k_head_mfma32<<<(unsigned)(need < 2048 ? need : 2048), 256, 0, s>>>((const __hip_bfloat16*)feats, ld, v2p, N, psc, psh, w1, b1, w2, b2, bb, lg, of);
       return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;

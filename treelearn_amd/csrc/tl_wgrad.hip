@@ -498,10 +498,6 @@ __global__ void k_wgrad_reduce(const float* __restrict__ ws, int64_t nparts, int
 
 }  // namespace
 
-static int g_wgrad_var = 0, g_wgrad_chunk = 0;   // developer A/B: kernel variant / fixed chunk rows
-static int g_wgrad_shared = 1;             // developer A/B (tl_dev_wgrad_mode bit 1): 0 = per-tap workgroups that gather gout per pair
-static int g_wgrad_bf16_mfma = 1;          // developer A/B (tl_dev_wgrad_mode): 0 = bf16 inputs through the fp32-MFMA kernel
-
 // tl_wgrad_dense.hip: the dense-over-taps form of the 27-tap convs of the big levels
 int tl_wgrad_dense_slots(int64_t n_out, int K, int Cin, int Cout);
 int tl_launch_wgrad_dense(const uint16_t* x, int64_t x_ld, const uint16_t* g, int64_t g_ld, const int32_t* table, int64_t n_out, int64_t n_in, int K, int Cin,
@@ -518,14 +514,6 @@ int64_t tl_wgrad_tinycout_parts(int64_t n);
 int tl_launch_wgrad_tinycout(const void* x, int64_t x_ld, const void* g, int64_t g_ld, int dtype, int64_t n, int Cin, int Cout, float* gw, float* ws, hipStream_t s);
 
 extern "C" {
-
-#ifdef TL_DEV
-int tl_dev_wgrad_mode(int mode) {
-  g_wgrad_bf16_mfma = mode & 1; g_wgrad_shared = !(mode & 2); g_wgrad_var = (mode >> 8) & 15;
-  g_wgrad_chunk = ((mode >> 12) & 3) ? 2048 << ((mode >> 12) & 3) : 0;
-  return TL_OK;
-}
-#endif
 
 int64_t tl_conv_wgrad_ws_floats(int64_t n_out, int K, int Cin, int Cout) {
   int64_t nparts = tl_cdiv(n_out, (int64_t)kRowsPerWave * kWaves) * kWaves;
@@ -548,7 +536,7 @@ static int wgrad_impl(const void* x, int64_t x_ld, const void* gout, int64_t g_l
   const int64_t nchunks = tl_cdiv(n_out, (int64_t)kRowsPerWave * kWaves);
   int64_t nchunks_used = nchunks;
   const bool bf16_mfma = dtype == TL_BF16 && Cout % 8 == 0 && Cin % 8 == 0 && x_ld % 8 == 0 && g_ld % 8 == 0 && ((uintptr_t)x) % 16 == 0 &&
-                         ((uintptr_t)gout) % 16 == 0 && g_wgrad_bf16_mfma;
+                         ((uintptr_t)gout) % 16 == 0;
   if (K == 1 && !table && Cout <= 4 && n_in == n_out) {
     const int rc = tl_launch_wgrad_tinycout(x, x_ld, gout, g_ld, dtype, n_out, Cin, Cout, gw, ws, s);
     if (rc != TL_ERR_UNSUPPORTED) return rc;
@@ -574,27 +562,16 @@ static int wgrad_impl(const void* x, int64_t x_ld, const void* gout, int64_t g_l
     const int to = wide ? 3 : (Cout > 32 ? 2 : 1), ti = wide ? 3 : (Cin > 32 ? 2 : 1);
     const int nbo = (int)tl_cdiv(Cout, 32 * to), nbi = (int)tl_cdiv(Cin, 32 * ti);
     const uint16_t* xb = (const uint16_t*)x; const uint16_t* gb = (const uint16_t*)gout;
-    if (K == 27 && to >= 2 && ti >= 2 && g_wgrad_shared) {
+    if (K == 27 && to >= 2 && ti >= 2) {
       // shared-gout form (27-tap convs with both sides >= 64 channels; 32-channel sides and the 8-tap down / up convs measured
       // slower in it): workgroup = (row chunk, 4 taps, block); chunks of 4 096 .. 16 384 rows (the workspace holds one partial per
       // 4 096 rows), the smallest that still gives every CU a few workgroups
       int64_t chunk = 16384;
-      if (g_wgrad_chunk) chunk = g_wgrad_chunk;
-      else while (chunk > 4096 && tl_cdiv(n_out, chunk) * tl_cdiv(K, kWaves) * nbo * nbi < 2048) chunk >>= 1;
+      while (chunk > 4096 && tl_cdiv(n_out, chunk) * tl_cdiv(K, kWaves) * nbo * nbi < 2048) chunk >>= 1;
       nchunks_used = tl_cdiv(n_out, chunk);
 #define TL_WS(O_, I_, T_, R_, ...)                                                                                          \
   k_wgrad_bf16s<O_, I_, T_, R_, ##__VA_ARGS__><<<dim3((unsigned)nchunks_used, (unsigned)tl_cdiv(K, kWaves * T_), (unsigned)(nbo * nbi)), kWaves * 64, 0, s>>>( \
       xb, x_ld, gb, g_ld, table, n_out, n_in, K, Cin, Cout, nbi, (int)chunk, ws)
-#ifdef TL_DEV
-      const int v = g_wgrad_var;                               // tools/dev_wgrad_var.py
-      if (v && to == 2) {
-        if (v == 1) TL_WS(2, 2, 1, 128, false, 0); else if (v == 2) TL_WS(2, 2, 1, 128, false, 2); else if (v == 3) TL_WS(2, 2, 1, 128, true, 0);
-        else if (v == 4) TL_WS(2, 2, 1, 128, true, 1); else if (v == 5) TL_WS(2, 2, 1, 128, true, 2); else if (v == 6) TL_WS(2, 2, 2, 128, true, 1);
-        else TL_WS(2, 2, 1, 256, true, 1);
-      } else if (v && to == 3) {
-        if (v == 1) TL_WS(3, 3, 1, 128, false, 1); else if (v == 3) TL_WS(3, 3, 1, 128, true, 0); else TL_WS(3, 3, 1, 128, false, 0);
-      } else
-#endif
       if (to == 3) TL_WS(3, 3, 1, 128, true, 1);              // level 3 (24 of 27 taps present): no pair compaction
       else TL_WS(2, 2, 1, 128, false, 1);
 #undef TL_WS

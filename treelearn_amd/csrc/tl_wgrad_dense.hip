@@ -697,7 +697,6 @@ int g_wgrad_dense = 1;            // tl_set_tuning("wgrad_dense", 0) restores th
 int64_t g_wgrad_dense_min_rows = 60000;
 
 // row slots (= partial tile sets) of the dense form for a shape, 0 if the shape is not served
-int g_wgrad_dense_gx = 0;          // tl_set_tuning("wgrad_dense_gx", n): slot count override (experiments)
 
 int tl_wgrad_dense_slots(int64_t n_out, int K, int Cin, int Cout) {
   if (!g_wgrad_dense || K != 27 || n_out < g_wgrad_dense_min_rows) return 0;
@@ -724,7 +723,6 @@ int tl_wgrad_dense_slots(int64_t n_out, int K, int Cin, int Cout) {
       case 256128: gx = 16; break;                         // 216 jobs: 16 workgroups per slot
     }
   }
-  if (gx && g_wgrad_dense_gx) gx = g_wgrad_dense_gx & ~7;
   return gx;
 }
 

@@ -7,7 +7,6 @@ generation (`subm1..7`, `spconv1..6`; blocks.py:57-70,104-123).  Two host syncs 
 the grid extent (3 ints) and the per-level voxel counts (L ints).
 """
 import ctypes
-import os
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -141,61 +140,6 @@ def level_shapes(shape1, num_levels):
     return shapes
 
 
-def _build_per_level(L, st, dev, pcoords, N, batch_size, extent, shapes, num_levels):
-    """The same pyramid through the per-level entry points (one call per kernel group and level; `TL_GEOM=per_level`, kept for
-    A/B runs and as the reference for tests of the two-call form)."""
-    # 2. occupancy bitmaps + popcount prefix sums for every level (no host involvement)
-    dims = [(batch_size,) + extent]
-    for _ in range(num_levels - 1):
-        d = dims[-1]
-        dims.append((d[0], (d[1] + 1) // 2, (d[2] + 1) // 2, (d[3] + 1) // 2))
-    nw = [_nwords(d) for d in dims]
-    bm_all = torch.empty(sum(nw), dtype=torch.int64, device=dev)
-    pf_all = torch.empty(sum(nw), dtype=torch.int32, device=dev)
-    counts = torch.empty(num_levels, dtype=torch.int32, device=dev)
-    scan_ws = torch.empty(int(L.tl_scan_ws_words(max(nw))), dtype=torch.int32, device=dev)
-    levels = []
-    off = 0
-    for li in range(num_levels):
-        bm = bm_all[off:off + nw[li]]; pf = pf_all[off:off + nw[li]]; off += nw[li]
-        if li == 0:
-            _hip.check(L.tl_bitmap_from_points(_hip.ptr(pcoords), N, _hip.dims4(dims[0]), _hip.ptr(bm), st), "tl_bitmap_from_points")
-        else:
-            _hip.check(L.tl_bitmap_down(_hip.ptr(levels[-1].bitmap), _hip.dims4(dims[li - 1]), _hip.dims3(shapes[li]),
-                                        _hip.ptr(bm), _hip.dims4(dims[li]), st), "tl_bitmap_down")
-        _hip.check(L.tl_bitmap_scan(_hip.ptr(bm), nw[li], _hip.ptr(pf), _hip.ptr(counts[li:li + 1]), _hip.ptr(scan_ws), st), "tl_bitmap_scan")
-        levels.append(Level(n=0, dims=dims[li], shape=shapes[li], bitmap=bm, prefix=pf))
-    ns = counts.tolist()                                   # host sync #2
-    for lv, n in zip(levels, ns):
-        lv.n = int(n)
-        if lv.n <= 0:
-            raise ValueError("sparse conv produced an empty level: output spatial shape reach zero!!!")
-
-    # 3. coords, v2p, rulebooks
-    for li, lv in enumerate(levels):
-        lv.coords = torch.empty((lv.n, 4), dtype=torch.int32, device=dev)
-        _hip.check(L.tl_expand_coords(_hip.ptr(lv.bitmap), _hip.ptr(lv.prefix), _hip.dims4(lv.dims), _hip.ptr(lv.coords), st), "tl_expand_coords")
-        lv.nbr = torch.empty((27, lv.n), dtype=torch.int32, device=dev)
-        # big levels also get the column form of their rulebook (40 instead of 108 B/voxel) for the kernels that read it; it rides on
-        # the table tensor as an attribute
-        ct = torch.empty((10, lv.n), dtype=torch.int32, device=dev) if lv.n >= COMPACT_MIN_ROWS else None
-        _hip.check(L.tl_rulebook_subm(_hip.ptr(lv.coords), lv.n, _hip.ptr(lv.bitmap), _hip.ptr(lv.prefix), _hip.dims4(lv.dims),
-                                      _hip.ptr(lv.nbr), _hip.ptr(ct), st), "tl_rulebook_subm")
-        if ct is not None:
-            lv.nbr._tl_compact = ct
-    for li in range(num_levels - 1):
-        f, c = levels[li], levels[li + 1]
-        f.child = torch.empty((8, c.n), dtype=torch.int32, device=dev)
-        f.parent = torch.empty(f.n, dtype=torch.int32, device=dev)
-        f.inv = torch.empty((8, f.n), dtype=torch.int32, device=dev)
-        _hip.check(L.tl_rulebook_down(_hip.ptr(c.coords), c.n, _hip.ptr(f.bitmap), _hip.ptr(f.prefix), _hip.dims4(f.dims), f.n,
-                                      _hip.ptr(f.child), _hip.ptr(f.parent), _hip.ptr(f.inv), st), "tl_rulebook_down")
-    v2p = torch.empty(N, dtype=torch.int64, device=dev)
-    _hip.check(L.tl_point_rank(_hip.ptr(pcoords), N, _hip.ptr(levels[0].bitmap), _hip.ptr(levels[0].prefix), _hip.dims4(levels[0].dims),
-                               _hip.ptr(v2p), st), "tl_point_rank")
-    return TileGeometry(levels=levels, v2p=v2p, n_points=N, batch_size=batch_size, pcoords=pcoords, _backing=[bm_all, pf_all])
-
-
 def build_geometry(coords: torch.Tensor, batch_ids: torch.Tensor, batch_size: int, voxel_size: float,
                    num_levels: int, spatial_shape: Optional[List[int]] = None, need_inverse: bool = True,
                    blocked: bool = False, ref_table: bool = False, blk_min_rows: int = None, nn_table: bool = False) -> TileGeometry:
@@ -230,9 +174,6 @@ def build_geometry(coords: torch.Tensor, batch_ids: torch.Tensor, batch_size: in
     if any(e > s for e, s in zip(extent, shape1)):
         raise ValueError(f"tile extent {extent} voxels exceeds spatial_shape {shape1}")
     shapes = level_shapes(shape1, num_levels)
-
-    if os.environ.get("TL_GEOM") == "per_level" and not blocked:
-        return _build_per_level(L, st, dev, pcoords, N, batch_size, extent, shapes, num_levels)
 
     # 2. occupancy bitmaps + popcount prefix sums for every level: one call, one backing allocation
     dims = [(batch_size,) + extent]
@@ -314,11 +255,9 @@ def build_geometry(coords: torch.Tensor, batch_ids: torch.Tensor, batch_size: in
         # The unit builder (instruction-bound, ~0.27 ms) runs on a side stream beside the rulebook kernels of the other levels -- when the
         # forward is on the DEFAULT stream (a lone forward: -0.15 ms).  Callers that keep several tiles in flight on their own streams
         # (util/pipeline.get_pointwise_preds, bench.py) already fill those gaps, and one more stream per tile in flight oversubscribes
-        # the hardware queues (measured: 7.23 -> 7.67 ms per tile with three tiles in flight).  TL_BLK_SIDE=0 / 1 forces either.
+        # the hardware queues (measured: 7.23 -> 7.67 ms per tile with three tiles in flight).
         main = torch.cuda.current_stream()
-        want_side = os.environ.get("TL_BLK_SIDE")
-        use_side = (main == torch.cuda.default_stream(dev)) if want_side is None else want_side != "0"
-        side = _side_stream(dev) if use_side else main
+        side = _side_stream(dev) if main == torch.cuda.default_stream(dev) else main
         side.wait_stream(main)
         with torch.cuda.stream(side):
             _hip.check(L.tl_blk_build(arr[0].bitmap, arr[0].prefix, _hip.dims4(levels[0].dims), n1, ctypes.byref(bk), b0 + 4 * bl["ws"], 2, _hip.stream()), "tl_blk_build")

@@ -11,8 +11,6 @@ through tl_conv_fwd's out / out2 / out3.  The skip concat is two column views of
 
 Per ResidualBlock (blocks.py:55-79):   t = conv1(x_act) [epilogue bn3+relu];  y = conv2(t) + i_branch(x_raw)
 Per UBlock (blocks.py:137-149):        blocks -> down conv -> child UBlock -> inverse conv -> tail blocks
-
-`TL_ENGINE=prologue` selects the older form (BN+ReLU applied as a gather-side prologue) for A/B runs.
 """
 import os
 
@@ -146,55 +144,6 @@ class _U:
         return self.tail[1].run(y_raw, y_act, lv.nbr, n, views)
 
 
-# ------------------------------------------------------------------------------------------- prologue form (A/B)
-class _ResPro:
-    def __init__(self, block, dtype):
-        cb = block.conv_branch
-        self.s0, self.h0 = _bn_affine(cb[0])
-        self.w1 = ops.pack_weight(cb[2].weight, dtype)
-        self.s3, self.h3 = _bn_affine(cb[3])
-        self.w2 = ops.pack_weight(cb[5].weight, dtype)
-        ib = block.i_branch[0]
-        self.w1x1 = None if isinstance(ib, nn.Identity) else ops.pack_weight(ib.weight, dtype)
-
-    def run(self, x, nbr, n, out=None):
-        t = ops.conv_fwd(x, self.w1, nbr, n, in_scale=self.s0, in_shift=self.h0, in_relu=True,
-                         out_scale=self.s3, out_shift=self.h3, out_relu=True)
-        res = x if self.w1x1 is None else ops.conv_fwd(x, self.w1x1, None, n)
-        return ops.conv_fwd(t, self.w2, nbr, n, out=out, residual=res)
-
-
-class _UPro:
-    def __init__(self, ub, dtype):
-        self.C = ub.nPlanes[0]
-        self.blocks = [_ResPro(b, dtype) for b in ub.blocks._modules.values()]
-        self.deeper = len(ub.nPlanes) > 1
-        if self.deeper:
-            self.sd, self.hd = _bn_affine(ub.conv[0]); self.wd = ops.pack_weight(ub.conv[2].weight, dtype)
-            self.u = _UPro(ub.u, dtype)
-            self.su, self.hu = _bn_affine(ub.deconv[0]); self.wu = ops.pack_weight(ub.deconv[2].weight, dtype)
-            self.tail = [_ResPro(b, dtype) for b in ub.blocks_tail._modules.values()]
-
-    def run(self, x, geom, li):
-        lv = geom.levels[li]
-        n, C = lv.n, self.C
-        if not self.deeper:
-            for b in self.blocks:
-                x = b.run(x, lv.nbr, n)
-            return x
-        cat = torch.empty((n, 2 * C), dtype=x.dtype, device=x.device)
-        for i, b in enumerate(self.blocks):
-            x = b.run(x, lv.nbr, n, out=cat[:, :C] if i == len(self.blocks) - 1 else None)
-        nxt = geom.levels[li + 1]
-        d = ops.conv_fwd(x, self.wd, lv.child, nxt.n, in_scale=self.sd, in_shift=self.hd, in_relu=True)
-        d = self.u.run(d, geom, li + 1)
-        ops.conv_fwd(d, self.wu, lv.inv, n, out=cat[:, C:], in_scale=self.su, in_shift=self.hu, in_relu=True)
-        x = cat
-        for b in self.tail:
-            x = b.run(x, lv.nbr, n)
-        return x
-
-
 class InferencePlan:
     """Folded BatchNorms + packed weights of one TreeLearn module, for one compute dtype."""
     def __init__(self, model, dtype, x3=False):
@@ -203,11 +152,10 @@ class InferencePlan:
         self.dtype = dtype
         self.device = model.input_conv[0].weight.device            # a plan belongs to one device (net._plan_ok: a replica on another device builds its own)
         self.x3 = bool(x3) and dtype == torch.float32
-        self.preact = os.environ.get("TL_ENGINE", "preact") != "prologue"
         prev, ops.PACK_X3 = ops.PACK_X3, self.x3
         try:
             self.w_in = ops.pack_weight(model.input_conv[0].weight, dtype)
-            self.unet = (_U if self.preact else _UPro)(model.unet, dtype)
+            self.unet = _U(model.unet, dtype)
         finally:
             ops.PACK_X3 = prev
         self.so, self.ho = _bn_affine(model.output_layer[0])
@@ -222,41 +170,37 @@ class InferencePlan:
         self.b2 = torch.cat([model.semantic_linear[3].bias.detach().float(), model.offset_linear[3].bias.detach().float()]).contiguous()
 
     def supports_blocked(self):
-        """Level 1 may live in the block-local row order (geometry.BlockedRulebook): the pre-activated engine of a 32-channel net in a 16-bit
+        """Level 1 may live in the block-local row order (geometry.BlockedRulebook): the engine of a 32-channel net in a 16-bit
         dtype or in the parity-fast mode (fp32 rows, split-bf16 contraction: tl_conv_blk_x3.hip; TL_BLK_X3=0 keeps that mode on the gather kernels)."""
         ok_dtype = self.dtype != torch.float32 or (self.x3 and os.environ.get("TL_BLK_X3", "1") != "0")
-        return self.preact and ok_dtype and self.unet.C == 32 and os.environ.get("TL_BLK", "1") != "0"
+        return ok_dtype and self.unet.C == 32 and os.environ.get("TL_BLK", "1") != "0"
 
     def run(self, voxel_feats, geom: TileGeometry, want_backbone=True, all_ones=False):
         """`all_ones`: the caller built voxel_feats as ones (use_feats = False, use_coords = False): the input conv then needs no gather."""
         lv = geom.levels[0]
         vf = voxel_feats.to(self.dtype).contiguous()
-        if self.preact:
-            # TL_NO_ONES_TABLE=1 (A/B knob: run the input conv on the general kernels): honoured where the canonical table exists; a blocked
-            # geometry built without it (the default all-ones inference) keeps the presence-mask form -- same result either way
-            ones = all_ones and (os.environ.get("TL_NO_ONES_TABLE") != "1" or (geom.blocked and lv.nbr_ref is None))
-            # block-local level 1: BatchNorm + ReLU of the blocks' first convs at staging, raw tensors only (TL_BLK_PRO=0: the two-view form)
-            staged = (geom.blocked and self.unet.deeper and self.unet.C == 32 and self.unet.tail[0].w1_halves is not None
-                      and os.environ.get("TL_BLK_PRO", "1") != "0")
-            in_views = [RAW()] if staged else [RAW(), ACT(self.unet.blocks[0].bn0)]
-            if geom.blocked and not ones:
-                # block-local level 1 with real input features: the input conv runs on the canonical table, its two views are
-                # carried into the block-local order (not the default configuration: the reference feeds ones)
-                if lv.nbr_ref is None:
-                    raise RuntimeError("a blocked geometry needs ref_table=True when the input features are not all ones")
-                # (the voxel features were averaged through the blocked v2p map, so they arrive in the new order)
-                xs = _conv_views(vf.index_select(0, lv.nbr.o2n.long()), self.w_in, lv.nbr_ref, lv.n, in_views)
-                perm = lv.nbr.perm.long()
-                xs = [t.index_select(0, perm) for t in xs]
-            else:
-                xs = _conv_views(vf, self.w_in, lv.nbr, lv.n, in_views, all_ones=ones)
-            if staged:
-                (x,) = self.unet.run_l1_staged(xs[0], geom, [RAW()])
-            else:
-                (x,) = self.unet.run(xs[0], xs[1], geom, 0, [RAW()])
+        # TL_NO_ONES_TABLE=1 (A/B knob: run the input conv on the general kernels): honoured where the canonical table exists; a blocked
+        # geometry built without it (the default all-ones inference) keeps the presence-mask form -- same result either way
+        ones = all_ones and (os.environ.get("TL_NO_ONES_TABLE") != "1" or (geom.blocked and lv.nbr_ref is None))
+        # block-local level 1: BatchNorm + ReLU of the blocks' first convs at staging, raw tensors only (TL_BLK_PRO=0: the two-view form)
+        staged = (geom.blocked and self.unet.deeper and self.unet.C == 32 and self.unet.tail[0].w1_halves is not None
+                  and os.environ.get("TL_BLK_PRO", "1") != "0")
+        in_views = [RAW()] if staged else [RAW(), ACT(self.unet.blocks[0].bn0)]
+        if geom.blocked and not ones:
+            # block-local level 1 with real input features: the input conv runs on the canonical table, its two views are
+            # carried into the block-local order (not the default configuration: the reference feeds ones)
+            if lv.nbr_ref is None:
+                raise RuntimeError("a blocked geometry needs ref_table=True when the input features are not all ones")
+            # (the voxel features were averaged through the blocked v2p map, so they arrive in the new order)
+            xs = _conv_views(vf.index_select(0, lv.nbr.o2n.long()), self.w_in, lv.nbr_ref, lv.n, in_views)
+            perm = lv.nbr.perm.long()
+            xs = [t.index_select(0, perm) for t in xs]
         else:
-            x = ops.conv_fwd(vf, self.w_in, lv.nbr, lv.n)
-            x = self.unet.run(x, geom, 0)
+            xs = _conv_views(vf, self.w_in, lv.nbr, lv.n, in_views, all_ones=ones)
+        if staged:
+            (x,) = self.unet.run_l1_staged(xs[0], geom, [RAW()])
+        else:
+            (x,) = self.unet.run(xs[0], xs[1], geom, 0, [RAW()])
         if x.shape[1] in ops.HEAD_WIDTHS:
             return ops.head_mlp(x, geom.v2p, self.so, self.ho, self.w1, self.b1, self.w2, self.b2, want_backbone)
         # head widths the fused kernel has no instantiation for (the reference accepts any `channels`): output_layer through

@@ -19,7 +19,7 @@ import torch
 from .. import _hip, ops
 
 MAX_CONTEXTS = int(os.environ.get("TL_EXEC_MAX_CONTEXTS", "8"))      # (device, stream) contexts -- each with its arena -- an executor keeps alive
-_ENV_DEFAULTS = (("TL_BLK_PRO", "1"), ("TL_NO_ONES_TABLE", "0"), ("TL_NO_COMPACT", "0"), ("TL_ENGINE", "preact"), ("TL_GEOM", ""), ("TL_EXEC", "1"))
+_ENV_DEFAULTS = (("TL_BLK_PRO", "1"), ("TL_NO_ONES_TABLE", "0"), ("TL_NO_COMPACT", "0"), ("TL_EXEC", "1"))
 KINDS = ("subm", "down", "inverse", "1x1", "input")
 
 
@@ -84,7 +84,7 @@ class Executor:
     @staticmethod
     def supported(plan, model):
         """The configurations tl_forward serves (everything else: the Python-driven engine)."""
-        if not plan.preact or not (2 <= model.num_blocks <= _hip.TL_MAX_LEVELS):
+        if not (2 <= model.num_blocks <= _hip.TL_MAX_LEVELS):
             return False
         if plan.unet.C not in ops.HEAD_WIDTHS or plan.w_in.shape[0] != 27:
             return False
@@ -250,9 +250,7 @@ class Executor:
             a.backbone = _hip.ptr(bb); a.logits = logits.data_ptr(); a.offsets = offsets.data_ptr()
             a.point_feats = input_feats.data_ptr() if self.needs_feats else None
             # the unit builder beside the other levels' rulebook kernels for a lone forward on the default stream (geometry.build_geometry's rule)
-            want_side = os.environ.get("TL_BLK_SIDE")
-            use_side = (stream == torch.cuda.default_stream(dev)) if want_side is None else want_side != "0"
-            if use_side:
+            if stream == torch.cuda.default_stream(dev):
                 from ..geometry import _side_stream
                 a.side_stream = _side_stream(dev).cuda_stream
             with ctx[2]:                                                   # (ctypes releases the GIL: two Python threads on one stream would share read-back buffer and arena)

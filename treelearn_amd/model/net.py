@@ -160,7 +160,7 @@ class TreeLearn(nn.Module):
         # only the tensors the backbone reads cross PCIe here (the reference's cuda_cast also ships every label /
         # mask / centre tensor of the batch, ~80 MB per tile that inference never touches; util/train.py:28-43)
         mask_rows = None
-        if return_loss and os.environ.get("TL_LOSS_ROWS", "1") != "0":
+        if return_loss:
             mask_rows = loss_mask_rows(batch['masks_sem'], batch['masks_off'])        # before anything is enqueued: no wait behind the forward
         backbone_output, v2p_map = self.forward_backbone(coords=batch['coords'], input_feats=batch['input_feats'],
                                                          batch_ids=batch['batch_ids'], batch_size=batch['batch_size'])
@@ -197,15 +197,13 @@ class TreeLearn(nn.Module):
         whatever `compute_dtype` says; outside autocast: `compute_dtype`.  float16 is served end to end: the conv / head units AND the
         training units (weight gradient, BatchNorm train forward / backward, epilogue reductions, row gather / scatter-add) are compiled a
         second time for IEEE half (csrc/tl_half.h, tl_f16_train.h), so the reference's `autocast(enabled=config.fp16)` + GradScaler step
-        (tools/training/train.py:32,40-44) runs in float16 here as it does there; under a bf16 autocast it runs bf16 (no scaler needed)."""
+        (tools/training/train.py:32,40-44) runs in float16 here as it does there; under a bf16 autocast it runs bf16 (no scaler needed).
+        The dtype is the same for training and inference; `training` is accepted for callers that name the mode."""
         dt = self.compute_dtype
         if torch.is_autocast_enabled():
             dt = torch.get_autocast_dtype("cuda") if hasattr(torch, "get_autocast_dtype") else torch.get_autocast_gpu_dtype()
             if dt not in (torch.float16, torch.bfloat16):
                 dt = torch.float32
-        training = (self.training or torch.is_grad_enabled()) if training is None else training
-        if dt == torch.float16 and training and os.environ.get("TL_F16_TRAIN", "1") == "0":
-            dt = torch.bfloat16                     # (A/B switch: a float16 training region on the bf16 kernels, as before round 5)
         return dt
 
     @cuda_cast
@@ -233,7 +231,7 @@ class TreeLearn(nn.Module):
                 _ag.new_pack_epoch()                                  # the packed copies of the last step are stale whether or not `_version` says so (fused optimizers)
                 self._plan = None                                     # ... and so is an eval plan once this step's optimizer has run (a model kept in .eval()
                                                                       # while it is fine-tuned never passes through train(), which drops the plan otherwise)
-            if torch.is_grad_enabled() and os.environ.get("TL_PACK_BATCH", "1") != "0":
+            if torch.is_grad_enabled():
                 self._refresh_packed(dtype)                           # every conv weight packed in one launch (once per training forward)
             try:                                                       # 16-bit: mixed precision as under the reference's autocast
                 x = self.output_layer(self.unet(self.input_conv(x)))
@@ -292,7 +290,7 @@ class TreeLearn(nn.Module):
             except AttributeError:
                 pass
         backbone_feats = gather_rows(backbone_output.features, v2p_map, cache)
-        if not (self.training and torch.is_grad_enabled() and backbone_feats.dtype in (torch.bfloat16, torch.float16) and os.environ.get("TL_HEAD_FP32") != "1"):
+        if not (self.training and torch.is_grad_enabled() and backbone_feats.dtype in (torch.bfloat16, torch.float16)):
             backbone_feats = backbone_feats.float()
         # mixed-precision TRAINING keeps the heads in bf16 like the backbone (the reference's autocast runs their nn.Linear layers in
         # half precision too; get_loss casts logits / offsets to fp32): half the traffic of the gather, the two MLPs and their backward

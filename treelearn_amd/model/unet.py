@@ -137,10 +137,10 @@ class UBlock(nn.Module):
                 for i in range(block_reps)))
 
     def forward(self, input):
-        from ..autograd import CAT_IN_PLACE, cat_views, get_stats, set_stats
+        from ..autograd import cat_views, get_stats, set_stats
         buf = None
         f = input.features
-        if len(self.nPlanes) > 1 and CAT_IN_PLACE and f.is_cuda and torch.is_grad_enabled() and f.requires_grad and self.training:
+        if len(self.nPlanes) > 1 and f.is_cuda and torch.is_grad_enabled() and f.requires_grad and self.training:
             # training: the skip concat (reference blocks.py:146) without its copy -- the encoder's last block and the inverse conv write
             # straight into the two column halves of one [n, 2C] buffer (what the inference engine does with its views)
             C = self.nPlanes[0]

@@ -175,7 +175,7 @@ def conv_fwd(x: torch.Tensor, w_packed: torch.Tensor, table, n_out: int, out: to
     return out
 
 
-WGRAD_BLK = os.environ.get("TL_WGRAD_BLK", "1") != "0"        # level 1 (block-local rows): the staged-unit weight gradient (tl_conv_wgrad_blk)
+WGRAD_BLK = True        # level 1 (block-local rows): the staged-unit weight gradient (tl_conv_wgrad_blk); tests set False for the plain table
 
 
 def _conv_wgrad_blk(x, g, rb, ref_layout):

@@ -274,8 +274,6 @@ def get_pointwise_preds(model, dataloader, config, logger=None, return_backbone_
     # yet; with the runtime's default of four the fourth tile's stream shares a queue and three in flight are faster: 7.69 vs 7.96 ms per tile)
     from .. import hw_queues
     nf = max(1, int(os.environ.get("TL_TILES_IN_FLIGHT", "4" if hw_queues() >= 8 else "3"))) if use_gpu else 1
-    if os.environ.get("TL_LOOP_PIPELINE", "1") == "0":
-        nf = 1
     cstreams = _compute_streams(nf) if (use_gpu and nf > 1) else []
     restore_bb = None
     if hasattr(model, "return_backbone_feats") and not return_backbone_feats:
@@ -324,9 +322,6 @@ def get_pointwise_preds(model, dataloader, config, logger=None, return_backbone_
                     if slot is not None:
                         e2 = torch.cuda.Event(); e2.record(cs if cs is not None else torch.cuda.current_stream())
                         ring.release(slot, e2)
-                    continue
-                if os.environ.get("TL_LOOP_PIPELINE", "1") == "0":           # A/B switch: read every tile back right away
-                    read_back(pos, batch, gbatch, output, None, slot)
                     continue
                 pending.append((pos, batch, gbatch, output, done, slot))
                 if len(pending) > nf:
