@@ -551,6 +551,35 @@ int tl_eval_partition(const double* xyz, const int64_t* gt, const int64_t* pred,
                       int64_t n_gt, const int64_t* pred_order, const int64_t* pred_start, int64_t n_pred, const int64_t* pairs, int64_t m,
                       const double* edges, int n_edges, int mode, int64_t* tp, int64_t* fp, int64_t* fn, double* norm, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ points against the plot outline (csrc/tl_hull.hip)
+ * Replaces `get_coords_within_shape` (tree_learn/util/pipeline.py:211-223: a shapely Point per point + a geopandas sjoin) on the
+ * polygon of `get_hull` (:256-265) and on the ring buffer of `get_hull_buffer` (:240-253), as tools/pipeline/pipeline.py:80-81,136-142,
+ * 168-169 call it.  The ring is f64[V,2], CLOSED (first vertex repeated last): segments (x1,y1) = ring[k], (x2,y2) = ring[k+1], k < V-1.
+ * Per point (x = row[0], y = row[1] of pts, f32 or f64, row stride ld elements), in f64, plain operators, no fma contraction:
+ *   bit 0 (strictly inside, even-odd): parity over segments of [(y1 > py) != (y2 > py) and px < x1 + (py - y1) * (x2 - x1) / (y2 - y1)];
+ *   bit 1 (distance < r): any segment with t = ((px-x1)*dx + (py-y1)*dy) / (dx*dx + dy*dy) clamped to [0, 1], qx = x1 + t*dx,
+ *     qy = y1 + t*dy, (px-qx)*(px-qx) + (py-qy)*(py-qy) < r*r  (dx = x2-x1, dy = y2-y1); never set when r = 0.
+ * Both bits equal that formula evaluated over every segment (numpy); the per-point work reads only the point's slab and cell lists.
+ * The grid struct below is host-filled: slabs of height slab_h from slab_lo cover the ring's y-range widened by pad; cells (nx x ny, edge h, from lo)
+ * cover the ring's box widened by r + pad, nx = ny = 0 when r = 0; pad = the rounding allowance of the pruning; cover_r2 = (r - 2 pad)^2,
+ * or 0 to skip the covered-cell shortcut.
+ * tl_ring_lists: count pass (cell_seg = slab_seg = NULL): cell_cnt i64[nx*ny], slab_cnt i64[nslab] ZEROED by the caller, incremented per
+ *   listed segment; fill pass: the same arrays holding the exclusive starts on entry (advanced as cursors), lists i32 written at them.
+ *   Order within a list is not deterministic and does not affect any bit.
+ * tl_ring_covered: covered u8[nx*ny] = 1 if the whole cell is within sqrt(cover_r2) of one listed segment (cell_start i64[nx*ny + 1]).
+ * tl_ring_classify: out u8[n]; slab_start i64[nslab + 1]. */
+typedef struct {
+  double lo[2], h, r, pad, cover_r2, slab_lo, slab_h;
+  int32_t nx, ny, nslab, reserved;
+} tl_ring_grid;
+int tl_ring_lists(const double* ring, int64_t V, const tl_ring_grid* grid, int64_t* cell_cnt, int64_t* slab_cnt, int32_t* cell_seg,
+                  int32_t* slab_seg, tl_stream_t stream);
+int tl_ring_covered(const double* ring, const tl_ring_grid* grid, const int64_t* cell_start, const int32_t* cell_seg, uint8_t* covered,
+                    tl_stream_t stream);
+int tl_ring_classify(const void* pts, int dtype_f64, int64_t ld, int64_t n, const double* ring, const tl_ring_grid* grid,
+                     const int64_t* slab_start, const int32_t* slab_seg, const int64_t* cell_start, const int32_t* cell_seg,
+                     const uint8_t* covered, uint8_t* out, tl_stream_t stream);
+
 
 /* ------------------------------------------------------------------ the whole eval-mode forward behind ONE call
  * Replaces, per batch of tiles, the body of `model(batch, return_loss=False)` of the reference's tile loop

@@ -174,8 +174,16 @@ PROTOTYPES = {
     "tl_knn_vote_grid": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _c.c_float * 3, _f32, _I3, _vp, _i64, _i32, _vp, _vp]),
     "tl_eval_contingency": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "tl_eval_partition": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "tl_ring_lists": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tl_ring_covered": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "tl_ring_classify": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 TL_EVAL_XY, TL_EVAL_Z = 0, 1
+
+
+class RingGrid(_c.Structure):              # tl_ring_grid
+    _fields_ = [("lo", _c.c_double * 2), ("h", _c.c_double), ("r", _c.c_double), ("pad", _c.c_double), ("cover_r2", _c.c_double),
+                ("slab_lo", _c.c_double), ("slab_h", _c.c_double), ("nx", _i32), ("ny", _i32), ("nslab", _i32), ("reserved", _i32)]
 
 _lib = None
 

@@ -425,8 +425,8 @@ def evaluate_forest(gt_coords, gt_labels, pred_coords, pred_labels, min_iou_for_
 
 
 # ------------------------------------------------------------------------------------------------ command line
-def load_points(path):
-    """N x 4 (x y z label) float64 from .npy, .npz ('points' [+ 'labels'], as the reference's load_data) or whitespace-separated .txt."""
+def _read_points(path):
+    """A float64 array from .npy, .npz ('points' [+ 'labels'] as a last column, as the reference's load_data) or whitespace-separated .txt."""
     if path.endswith(".npy"):
         data = np.load(path)
     elif path.endswith(".npz"):
@@ -438,7 +438,12 @@ def load_points(path):
         data = np.loadtxt(path, ndmin=2)
     else:
         raise ValueError(f"{path}: expected .npy, .npz or .txt")
-    data = np.asarray(data, np.float64)
+    return np.asarray(data, np.float64)
+
+
+def load_points(path):
+    """N x 4 (x y z label) float64 from .npy, .npz ('points' [+ 'labels'], as the reference's load_data) or whitespace-separated .txt."""
+    data = _read_points(path)
     if data.ndim != 2 or data.shape[1] != 4:
         raise ValueError(f"{path}: expected N x 4 (x y z label), got {data.shape}")
     return data
