@@ -89,14 +89,14 @@ def test_exec_without_backbone_and_repeated_calls_reuse_the_arena():
     m = _model(torch.bfloat16)
     out_c, out_p, ex = _both(m, gb)
     _assert_equal(out_c, out_p)
-    arena = next(iter(ex._ctx.values()))[1]
+    arena = next(iter(ex._ctx.values())).arena
     ptr0, size0 = arena.data_ptr(), arena.numel()
     assert ex.last["arena_bytes"] <= size0
     m.return_backbone_feats = False
     with torch.no_grad():
         o2 = m(gb, return_loss=False)
     assert o2["backbone_feats"] is None and torch.equal(o2["offset_predictions"], out_c["offset_predictions"])
-    arena = next(iter(ex._ctx.values()))[1]
+    arena = next(iter(ex._ctx.values())).arena
     assert (arena.data_ptr(), arena.numel()) == (ptr0, size0)
     # a larger tile grows the arena, results stay right
     gb2 = _batch([make_tile(extent=20.0, voxel=0.1, n_trees=14, fill=0.1, seed=11)])
@@ -361,10 +361,10 @@ def test_exec_contexts_are_bounded_and_forty_streams_do_not_grow_memory():
             peak_ctx = max(peak_ctx, len(ex._ctx))
             mem.append(torch.cuda.memory_allocated())
     assert peak_ctx <= E.MAX_CONTEXTS and len(ex._ctx) == E.MAX_CONTEXTS
-    arena = next(iter(ex._ctx.values()))[1].numel()
+    arena = next(iter(ex._ctx.values())).arena.numel()
     assert max(mem[E.MAX_CONTEXTS:]) - mem[E.MAX_CONTEXTS - 1] < arena, "memory kept growing after the context cap was reached"
     ex.release_memory()
-    assert all(c[1] is None for c in ex._ctx.values())
+    assert all(c.arena is None for c in ex._ctx.values())
     with torch.no_grad():
         _assert_equal(m(gb, return_loss=False), ref)                        # arenas come back on demand
 
@@ -444,3 +444,147 @@ def test_tl_forward_rejects_inconsistent_descriptors():
     for i, f in enumerate(bad):
         assert call(mutated(f)) == _hip.TL_ERR_ARG, i
     L.tl_exec_destroy(ctx)
+
+
+# ------------------------------------------------------------------------------------------------ the life cycle of a context (executor._Context)
+def _ctx_of(ex, stream):
+    return ex._ctx.get((torch.cuda.current_device(), stream.cuda_stream))
+
+
+def _forward_on(m, gb, stream):
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.no_grad(), torch.cuda.stream(stream):
+        out = m(gb, return_loss=False)
+    stream.synchronize()
+    return out
+
+
+def test_evicted_contexts_are_dead_and_skipped():
+    """A context that the LRU rule evicted has left the registry, its handle is gone (`handle is None`) and so is its arena; check(),
+    release_memory() and profile() walk the live ones only, and check(stream=<an evicted stream>) has nothing to ask."""
+    from treelearn_amd.model import executor as E
+    from treelearn_amd.synth import make_tile
+    gb = _batch([make_tile(extent=12.0, voxel=0.1, n_trees=6, fill=0.1, seed=2)])
+    m = _model(torch.bfloat16)
+    with torch.no_grad():
+        ref = m(gb, return_loss=False)
+    ex = m._plan._exec
+    streams = [torch.cuda.Stream() for _ in range(3 + E.MAX_CONTEXTS)]
+    assert len({s.cuda_stream for s in streams}) == len(streams)
+    first = []
+    for s in streams[:3]:
+        _assert_equal(_forward_on(m, gb, s), ref)
+        first.append(_ctx_of(ex, s))
+    assert all(c is not None and c.handle is not None and c.arena is not None for c in first)
+    for s in streams[3:]:                                           # MAX_CONTEXTS younger ones: the default stream's and the first three go
+        _assert_equal(_forward_on(m, gb, s), ref)
+    assert len(ex._ctx) == E.MAX_CONTEXTS
+    live = list(ex._ctx.values())
+    for c in first:
+        assert c.handle is None and c.arena is None and c.pins == 0 and all(c is not v for v in live)
+    assert all(c.handle is not None for c in live)
+    ex.check()
+    ex.profile(True); ex.profile(False)
+    ex.release_memory()
+    assert all(c.arena is None and c.handle is not None for c in ex._ctx.values())
+    ex.check(stream=streams[0])                                     # no context of that stream any more: a no-op, and none is made for it
+    assert _ctx_of(ex, streams[0]) is None and list(ex._ctx.values()) == live
+    _assert_equal(_forward_on(m, gb, streams[0]), ref)              # a forward on the evicted stream starts over with a context of its own
+    assert _ctx_of(ex, streams[0]) is not first[0] and first[0].handle is None
+
+
+def test_eviction_that_raises_cleans_up(monkeypatch):
+    """The verdict of an evicted context's earlier forwards is asked on its way out (tl_exec_check).  When that raises, the exception
+    reaches the caller of the forward that evicted -- after EVERY context chosen for eviction has been ended, with no pin and no lock
+    left behind -- and the next forward on the same stream runs as usual."""
+    from treelearn_amd.model import executor as E
+    from treelearn_amd.synth import make_tile
+    gb = _batch([make_tile(extent=12.0, voxel=0.1, n_trees=6, fill=0.1, seed=2)])
+    m = _model(torch.bfloat16)
+    with torch.no_grad():
+        ref = m(gb, return_loss=False)
+    ex = m._plan._exec
+    streams = [torch.cuda.Stream() for _ in range(E.MAX_CONTEXTS)]
+    assert len({s.cuda_stream for s in streams}) == len(streams)
+    for s in streams[:-1]:                                          # the default stream's context + MAX_CONTEXTS - 1: the registry is full
+        _assert_equal(_forward_on(m, gb, s), ref)
+    before = list(ex._ctx.values())
+    assert len(before) == E.MAX_CONTEXTS
+    monkeypatch.setattr(E, "MAX_CONTEXTS", E.MAX_CONTEXTS - 2)      # the next new context has to evict three, the first of which "reports"
+    real, calls = E.Executor._raise_if_flagged, []
+
+    def raise_once(rc):
+        calls.append(rc)
+        if len(calls) == 1:
+            raise RuntimeError("injected verdict of an evicted context")
+        return real(rc)
+
+    monkeypatch.setattr(E.Executor, "_raise_if_flagged", staticmethod(raise_once))
+    with pytest.raises(RuntimeError, match="injected verdict of an evicted context"):
+        _forward_on(m, gb, streams[-1])
+    assert len(calls) == 3 and len(ex._ctx) <= E.MAX_CONTEXTS
+    live = list(ex._ctx.values())
+    for c in live:
+        assert c.pins == 0 and c.handle is not None
+        assert c.lock.acquire(blocking=False)
+        c.lock.release()
+    evicted = [c for c in before if all(c is not v for v in live)]
+    assert len(evicted) == 3 and evicted == before[:3]              # least recently used first
+    for c in evicted:
+        assert c.handle is None and c.arena is None and c.pins == 0
+        assert c.lock.acquire(blocking=False)
+        c.lock.release()
+    _assert_equal(_forward_on(m, gb, streams[-1]), ref)
+    assert len(calls) == 3 and len(ex._ctx) <= E.MAX_CONTEXTS
+
+
+def test_arena_freed_by_the_finaliser_is_withheld_until_its_stream_is_done():
+    """The arena of a forward on a side stream comes out of the DEFAULT stream's allocator pool.  When the plan is dropped while that
+    stream is still busy (load_state_dict, train(), invalidate_plan, a collected model: only Executor.__del__ runs), the block must not be
+    handed to a default-stream allocation before the side stream is done with it.  The allocator cache is emptied first, so the arena's
+    block is the one exact fit for the probe allocation: without the stream-ordered free the probe gets the arena's address.
+
+    The finaliser frees the arena and then destroys the handle, and `tl_exec_destroy` waits for the whole device (hipHostFree of the
+    read-back buffer synchronises implicitly): by the time `invalidate_plan()` returns, the side stream has drained however long it was kept
+    busy.  The probe allocation is therefore made from a second thread while the main thread is inside the finaliser: it waits until the
+    context has let go of its arena (Python-side state only), allocates, and notes whether the side stream was still busy right after."""
+    import gc, threading, time, weakref
+    from treelearn_amd.synth import make_tile
+    gb = _batch([make_tile(extent=12.0, voxel=0.1, n_trees=6, fill=0.1, seed=2)])
+    m = _model(torch.bfloat16)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter(); torch.cuda._sleep(100_000_000); torch.cuda.synchronize()
+    cycles = int(100_000_000 * 1.0 / (time.perf_counter() - t0))   # about a second of busy-wait
+    s = torch.cuda.Stream()
+    m.ensure_plan()
+    gc.collect(); torch.cuda.synchronize(); torch.cuda.empty_cache()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.no_grad(), torch.cuda.stream(s):
+        m(gb, return_loss=False)
+        torch.cuda._sleep(cycles)
+    ex = m._plan._exec
+    ctx = _ctx_of(ex, s)
+    ptr, size = ctx.arena.data_ptr(), ctx.arena.numel()
+    gone = weakref.ref(ex)
+    seen = {}
+
+    def probe_while_the_finaliser_runs():
+        deadline = time.perf_counter() + 30.0
+        while ctx.arena is not None and time.perf_counter() < deadline:
+            time.sleep(0.001)
+        seen["freed"] = ctx.arena is None
+        seen["probe"] = torch.empty(size, dtype=torch.uint8, device="cuda")     # this thread's current stream: the default stream
+        seen["busy"] = not s.query()
+
+    th = threading.Thread(target=probe_while_the_finaliser_runs)
+    th.start()
+    del ex
+    m.invalidate_plan()                                             # nothing is synchronised by this test: Executor.__del__ is all that runs
+    gc.collect()
+    th.join()
+    assert gone() is None and seen["freed"] and ctx.handle is None
+    assert seen["busy"], "the side stream drained before the probe allocation: lengthen the busy-wait"
+    assert seen["probe"].data_ptr() != ptr, "the arena's block was handed out while kernels on its stream were still in flight"
+    s.synchronize()
+    seen.clear()
+    torch.empty(size, dtype=torch.uint8, device="cuda")             # (now the block may come back)

@@ -152,6 +152,7 @@ class InferencePlan:
         self.dtype = dtype
         self.device = model.input_conv[0].weight.device            # a plan belongs to one device (net._plan_ok: a replica on another device builds its own)
         self.x3 = bool(x3) and dtype == torch.float32
+        self._exec = None                                          # the C-side forward executor of this plan where tl_forward serves the model (net._plan_for)
         prev, ops.PACK_X3 = ops.PACK_X3, self.x3
         try:
             self.w_in = ops.pack_weight(model.input_conv[0].weight, dtype)

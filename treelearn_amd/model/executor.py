@@ -10,6 +10,7 @@ tree_learn.py:18: voxel-mean features) on the pre-activated engine with every de
 Python-driven engine (`supported()`), which issues the same launches -- results are bit-identical (tests/test_gpu_exec.py).
 """
 import collections
+import contextlib
 import ctypes
 import os
 import threading
@@ -38,6 +39,48 @@ def _res(dst, b):
     _aff(dst.bn0, b.bn0); _wt(dst.w1, b.w1); _aff(dst.bn3, b.bn3); _wt(dst.w2, b.w2); _wt(dst.w1x1, b.w1x1)
     if b.w1_halves is not None:
         _wt(dst.w1_half[0], b.w1_halves[0]); _wt(dst.w1_half[1], b.w1_halves[1])
+
+
+class _Context:
+    """The native handle (`tl_exec*`) and the arena of the forwards on one (device, stream).
+
+    Life cycle, driven by `Executor._pinned`: created and registered under the executor's registry lock; pinned (`pins`, guarded by that same
+    lock) by whoever is about to use it; used under its own `lock` (one forward at a time per context); unpinned; ended -- by an eviction,
+    which only takes a context that nobody has pinned, or by the executor's finaliser.  `handle is None`: ended."""
+    __slots__ = ("handle", "arena", "lock", "pins", "device", "stream")
+
+    def __init__(self, device, stream):
+        self.handle = _hip.lib().tl_exec_create()
+        if not self.handle:
+            raise RuntimeError("tl_exec_create failed")
+        self.arena = None
+        self.lock = threading.Lock()
+        self.pins = 0
+        self.device, self.stream = device, stream
+
+    def new_arena(self, nbytes):
+        """Arenas come out of the DEFAULT stream's pool of torch's caching allocator whatever stream the forward runs on: freed blocks of
+        evicted / shrunk arenas are then reusable by every other context instead of staying cached per stream handle.  The allocator is told
+        at once which stream uses the block, so however the tensor dies (grow, shrink, release_memory, eviction, the executor's finaliser,
+        interpreter exit), the block is withheld until the kernels enqueued on that stream by then have finished."""
+        self.arena = None                                              # the old block goes back before the new one is asked for
+        d0 = torch.cuda.default_stream(self.device)
+        if self.stream == d0:
+            self.arena = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            return
+        with torch.cuda.stream(d0):
+            self.arena = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.stream.wait_stream(d0)                                    # the block's previous owner may still be running on the default stream
+        self.arena.record_stream(self.stream)
+
+    def drop_arena(self):
+        self.arena = None
+
+    def end(self):
+        self.drop_arena()
+        handle, self.handle = self.handle, None
+        if handle is not None:
+            _hip.lib().tl_exec_destroy(handle)
 
 
 class Executor:
@@ -77,7 +120,7 @@ class Executor:
         d.head_w1 = plan.w1.data_ptr(); d.head_b1 = plan.b1.data_ptr(); d.head_w2 = plan.w2.data_ptr(); d.head_b2 = plan.b2.data_ptr()
         self.head_C = u_top_C = plan.unet.C
         assert u_top_C in ops.HEAD_WIDTHS
-        self._ctx = collections.OrderedDict()      # (device index, stream handle) -> [tl_exec*, arena tensor, lock], least recently used first
+        self._ctx = collections.OrderedDict()      # (device index, stream handle) -> _Context, least recently used first
         self._ctx_lock = threading.Lock()
         self.profiling = False
 
@@ -99,76 +142,65 @@ class Executor:
 
     def __del__(self):
         try:
-            L = _hip.lib()
             for c in self._ctx.values():
-                L.tl_exec_destroy(c[0])
+                c.end()
         except Exception:                                        # noqa: BLE001  (interpreter shutdown)
             pass
 
-    def release_memory(self):
-        """Drop the arenas (they are re-allocated by the next forward).  Waits for a forward that is inside the library on another thread."""
-        with self._ctx_lock:
-            ctxs = list(self._ctx.items())
-        for k, c in ctxs:
-            with c[2]:
-                self._drop_arena(c, torch.cuda.ExternalStream(k[1], device=torch.device("cuda", k[0])) if k[1] else None)
+    @contextlib.contextmanager
+    def _pinned(self, dev=None, stream=None, create=False):
+        """The one way to a context: looks up under the registry lock, pins, yields a list -- the context of (dev, stream), every context
+        when `stream` is None -- and unpins.  A pinned context is not evicted, so its handle stays alive for the caller, who takes the
+        context's own `lock` around every call into the library.
 
-    def _context(self, dev, stream, pin=False):
-        """The (device, stream) context, most recently used last.  Beyond MAX_CONTEXTS the least recently used one that no thread is inside
-        goes: its arena returns to torch's allocator (stream-ordered: kernels already enqueued on its stream finish first), its handle is
-        destroyed.  A caller that runs every request on a fresh stream therefore holds MAX_CONTEXTS arenas, not one per stream it ever used."""
-        key = (dev.index, stream.cuda_stream)
-        evicted = []
+        `create`: the context is made if it is missing and becomes the most recently used one.  Beyond MAX_CONTEXTS the least recently used
+        contexts that no thread has pinned (a locked one is always pinned) go: their arenas return to torch's allocator (stream-ordered:
+        kernels already enqueued on their streams finish first), their handles are destroyed.  A caller that runs every request on a fresh
+        stream therefore holds MAX_CONTEXTS arenas, not one per stream it ever used.  The verdict of an evicted context's forwards is asked
+        on its way out; if one reports, the error is raised once all of them are ended and the caller's pin is released."""
+        flagged = None
         with self._ctx_lock:
-            c = self._ctx.get(key)
-            if c is None:
-                ex = _hip.lib().tl_exec_create()
-                if not ex:
-                    raise RuntimeError("tl_exec_create failed")
-                c = self._ctx[key] = [ex, None, threading.Lock(), 0]   # handle, arena, a lock (one forward at a time per context), callers holding it
+            if stream is None:
+                ctxs = list(self._ctx.values())
             else:
-                self._ctx.move_to_end(key)
-            if pin:
-                c[3] += 1                                              # (released by the caller through _unpin: an eviction must not take a context
-                                                                       #  between this look-up and the caller's acquisition of its lock)
-            if len(self._ctx) > max(MAX_CONTEXTS, 1):
-                for k in list(self._ctx.keys()):
+                key = (dev.index, stream.cuda_stream)
+                c = self._ctx.get(key)
+                if c is None and create:
+                    c = self._ctx[key] = _Context(dev, stream)
+                elif create:
+                    self._ctx.move_to_end(key)
+                ctxs = [c] if c is not None else []
+            for c in ctxs:
+                c.pins += 1
+            if create and len(self._ctx) > max(MAX_CONTEXTS, 1):
+                for k, old in list(self._ctx.items()):
                     if len(self._ctx) <= max(MAX_CONTEXTS, 1):
                         break
-                    old = self._ctx[k]
-                    if k != key and old[3] == 0 and old[2].acquire(blocking=False):   # (a context another thread holds or runs a forward on stays)
-                        del self._ctx[k]
-                        evicted.append((k, old))
-        for k, old in evicted:
-            try:
-                self._raise_if_flagged(_hip.lib().tl_exec_check(old[0]))
-            finally:
-                self._drop_arena(old, torch.cuda.ExternalStream(k[1], device=torch.device("cuda", k[0])) if k[1] else None)
-                _hip.lib().tl_exec_destroy(old[0])
-                old[2].release()
-        return c
+                    if old.pins:                                         # (a context another thread holds or runs a forward on stays)
+                        continue
+                    del self._ctx[k]                                     # under the registry lock: in the registry <=> alive
+                    try:
+                        self._raise_if_flagged(_hip.lib().tl_exec_check(old.handle))
+                    except Exception as e:                               # noqa: BLE001  (raised below, once every evicted context is ended)
+                        flagged = flagged or e
+                    finally:
+                        old.end()
+        try:
+            if flagged is not None:
+                raise flagged
+            yield ctxs
+        finally:
+            flagged = None                                               # (its traceback holds this frame: no cycle that keeps the executor alive)
+            with self._ctx_lock:
+                for c in ctxs:
+                    c.pins -= 1
 
-    def _unpin(self, c):
-        with self._ctx_lock:
-            c[3] -= 1
-
-    @staticmethod
-    def _new_arena(nbytes, dev, stream):
-        """Arenas come out of the DEFAULT stream's pool of torch's caching allocator whatever stream the forward runs on: freed blocks of
-        evicted / shrunk arenas are then reusable by every other context instead of staying cached per stream handle."""
-        d0 = torch.cuda.default_stream(dev)
-        if stream == d0:
-            return torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        with torch.cuda.stream(d0):
-            t = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        stream.wait_stream(d0)                                         # the block's previous owner may still be running on the default stream
-        return t
-
-    @staticmethod
-    def _drop_arena(ctx, stream):
-        t, ctx[1] = ctx[1], None
-        if t is not None and stream is not None and stream != torch.cuda.default_stream(t.device):
-            t.record_stream(stream)                                    # kernels of this context's stream may still be reading / writing it
+    def release_memory(self):
+        """Drop the arenas (they are re-allocated by the next forward).  Waits for a forward that is inside the library on another thread."""
+        with self._pinned() as ctxs:
+            for c in ctxs:
+                with c.lock:
+                    c.drop_arena()
 
     @staticmethod
     def _raise_if_flagged(rc):
@@ -184,30 +216,27 @@ class Executor:
         of waiting for the tile's geometry)."""
         if stream is not None:
             dev = dev or torch.device("cuda", torch.cuda.current_device())
-            with self._ctx_lock:
-                c = self._ctx.get((dev.index, stream.cuda_stream))
-            ctxs = [c] if c is not None else []
-        else:
-            with self._ctx_lock:
-                ctxs = list(self._ctx.values())
-        for c in ctxs:
-            with c[2]:
-                self._raise_if_flagged(_hip.lib().tl_exec_check(c[0]))
+        with self._pinned(dev, stream) as ctxs:
+            for c in ctxs:
+                with c.lock:
+                    self._raise_if_flagged(_hip.lib().tl_exec_check(c.handle))
 
     def profile(self, enable):
         """Live per-launch HIP-event timing of the following forwards (bench.py's roofline pass)."""
         self.profiling = bool(enable)
-        for c in self._ctx.values():
-            _hip.lib().tl_exec_profile(c[0], int(self.profiling))
+        with self._pinned() as ctxs:
+            for c in ctxs:
+                with c.lock:
+                    _hip.lib().tl_exec_profile(c.handle, int(self.profiling))
 
     def profile_read(self, dev=None, stream=None):
         """Launch records of the last profiled forward on the current stream: list of dicts (level, kind, K, Cin, Cout, n_out, n_in, residual, esize,
         split, in_scale, ms)."""
         stream = stream or torch.cuda.current_stream()
         dev = dev or torch.device("cuda", torch.cuda.current_device())
-        ex = self._context(dev, stream)[0]
         buf = (_hip.LaunchRec * 512)()
-        n = _hip.lib().tl_exec_profile_read(ex, buf, 512)
+        with self._pinned(dev, stream, create=True) as (ctx,), ctx.lock:
+            n = _hip.lib().tl_exec_profile_read(ctx.handle, buf, 512)
         if n < 0:
             _hip.check(n, "tl_exec_profile_read")
         out = []
@@ -234,10 +263,9 @@ class Executor:
             raise ValueError("empty tile")
         dev = coords.device
         stream = torch.cuda.current_stream(dev)
-        ctx = self._context(dev, stream, pin=True)
-        try:
+        with self._pinned(dev, stream, create=True) as (ctx,):
             if self.profiling:
-                L.tl_exec_profile(ctx[0], 1)
+                L.tl_exec_profile(ctx.handle, 1)
             plan = self._plan_ref()
             if plan is None:
                 raise RuntimeError("the InferencePlan of this executor is gone")
@@ -253,23 +281,20 @@ class Executor:
             if stream == torch.cuda.default_stream(dev):
                 from ..geometry import _side_stream
                 a.side_stream = _side_stream(dev).cuda_stream
-            with ctx[2]:                                                   # (ctypes releases the GIL: two Python threads on one stream would share read-back buffer and arena)
+            with ctx.lock:                                                 # (ctypes releases the GIL: two Python threads on one stream would share read-back buffer and arena)
                 for attempt in range(4):
-                    if ctx[1] is None:
-                        ctx[1] = self._new_arena(max(1 << 20, int(N * 1536)), dev, stream)                    # first guess: ~1.5 KB per point
-                    a.arena = ctx[1].data_ptr(); a.arena_bytes = ctx[1].numel()
-                    rc = L.tl_forward(ctx[0], ctypes.byref(self.desc), ctypes.byref(a), stream.cuda_stream)
+                    if ctx.arena is None:
+                        ctx.new_arena(max(1 << 20, int(N * 1536)))                                            # first guess: ~1.5 KB per point
+                    a.arena = ctx.arena.data_ptr(); a.arena_bytes = ctx.arena.numel()
+                    rc = L.tl_forward(ctx.handle, ctypes.byref(self.desc), ctypes.byref(a), stream.cuda_stream)
                     if rc != _hip.TL_ERR_ARENA:
                         break
-                    self._drop_arena(ctx, stream)                          # grow: the exact figure when the level counts were known, a guess before that
-                    ctx[1] = self._new_arena(int(a.needed_bytes * 1.15) + (1 << 20), dev, stream)
+                    ctx.new_arena(int(a.needed_bytes * 1.15) + (1 << 20))  # grow: the exact figure when the level counts were known, a guess before that
                 # an arena far larger than this context's tiles need (a one-off big tile) goes back: the next forward allocates what it needs
-                if rc == _hip.TL_OK and ctx[1].numel() > 4 * int(a.needed_bytes) + (64 << 20):
-                    self._drop_arena(ctx, stream)
+                if rc == _hip.TL_OK and ctx.arena.numel() > 4 * int(a.needed_bytes) + (64 << 20):
+                    ctx.drop_arena()
                 if rc == _hip.TL_OK and os.environ.get("TL_EXEC_CHECK") == "1":
-                    rc = L.tl_exec_check(ctx[0])                             # per-tile verdict of the unit builder's assertion (waits for this tile's geometry)
-        finally:
-            self._unpin(ctx)
+                    rc = L.tl_exec_check(ctx.handle)                         # per-tile verdict of the unit builder's assertion (waits for this tile's geometry)
         if rc == _hip.TL_ERR_BLK:
             self._raise_if_flagged(rc)
         if rc == _hip.TL_ERR_REACH_ZERO:

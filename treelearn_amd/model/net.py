@@ -75,9 +75,27 @@ class TreeLearn(nn.Module):
         """Build the fused inference plan (folded BatchNorms, packed weights) now, on the current stream.  Callers that spread
         forwards over several streams do this first: the plan is otherwise built by the first forward, on that forward's stream,
         and a forward on another stream could read weights that are still being packed."""
-        if not self.training and (self._plan is None or not self._plan_ok(self.active_dtype(False))):
-            self._plan = InferencePlan(self, self.active_dtype(False), x3=self.split_bf16)
+        if not self.training:
+            self._plan_for(self.active_dtype(False))
         return self
+
+    def _plan_for(self, dtype):
+        """The valid InferencePlan for `dtype` (`_plan_ok`), built now if there is none; with it the C-side forward executor
+        (model/executor.py) where tl_forward serves this configuration."""
+        if not self._plan_ok(dtype):
+            from .executor import Executor
+            plan = InferencePlan(self, dtype, x3=self.split_bf16)
+            if Executor.supported(plan, self):
+                plan._exec = Executor(plan, self)
+            self._plan = plan
+        return self._plan
+
+    def check_forwards(self):
+        """Report the block-local unit builder's verdict for every eval forward enqueued so far (Executor.check: raises if one of them
+        skipped units); nothing to ask when the forwards do not go through tl_forward."""
+        ex = self._plan._exec if self._plan is not None else None
+        if ex is not None:
+            ex.check()
 
     def _refresh_packed(self, dtype):
         """Training: all conv weights -> kernel layouts in ONE launch when any parameter changed (autograd.PackPlan), instead of three small
@@ -138,11 +156,7 @@ class TreeLearn(nn.Module):
         """The C-side forward executor of the current plan (model/executor.py), or None when this configuration stays on the
         Python-driven engine."""
         from .executor import Executor
-        if self._plan is None or not self._plan_ok(dtype):
-            self._plan = InferencePlan(self, dtype, x3=self.split_bf16)
-        ex = getattr(self._plan, "_exec", False)
-        if ex is False:
-            ex = self._plan._exec = Executor(self._plan, self) if Executor.supported(self._plan, self) else None
+        ex = self._plan_for(dtype)._exec
         return ex if (ex is not None and Executor.env_default()) else None
 
     def forward(self, batch, return_loss):
@@ -210,8 +224,8 @@ class TreeLearn(nn.Module):
     def forward_backbone(self, coords, input_feats, batch_ids, batch_size, **kwargs):
         dtype = self.active_dtype()
         fused = not (self.training or torch.is_grad_enabled())
-        if fused and (self._plan is None or not self._plan_ok(dtype)):
-            self._plan = InferencePlan(self, dtype, x3=self.split_bf16)
+        if fused:
+            self._plan_for(dtype)
         # training under mixed precision: level 1 in the block-local order too (the staged-unit kernel serves its 32 -> 32 forward and
         # input-gradient convs; weight gradients and the other widths read the plain table in the new order, BlockedRulebook.nn_table)
         blk_train = (not fused and dtype in (torch.bfloat16, torch.float16) and self.unet.nPlanes[0] == 32 and os.environ.get("TL_BLK", "1") != "0"
@@ -246,8 +260,7 @@ class TreeLearn(nn.Module):
         Returns a handle for `infer`.  Calling `prepare(next_tile)` right after `infer(this_tile)` lets the next tile's
         geometry (small latency-bound kernels + two host syncs) run while this tile's convs occupy the main stream."""
         assert not self.training, "prepare/infer is the eval-mode fused path"
-        if self._plan is None or not self._plan_ok(self.active_dtype(False)):
-            self._plan = InferencePlan(self, self.active_dtype(False), x3=self.split_bf16)
+        self._plan_for(self.active_dtype(False))
         if self._geom_stream is None:
             self._geom_stream = torch.cuda.Stream()
         main = torch.cuda.current_stream()

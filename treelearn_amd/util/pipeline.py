@@ -330,9 +330,8 @@ def get_pointwise_preds(model, dataloader, config, logger=None, return_backbone_
                 read_back(*pnd)
             # the unit builder's assertion flag of a tile's forward is otherwise only seen by the NEXT forward on the same stream: after the last
             # tile, ask for it (every tile's results have been read back, so nothing waits here)
-            ex = getattr(getattr(model, "_plan", None), "_exec", None)
-            if ex:
-                ex.check()
+            if hasattr(model, "check_forwards"):
+                model.check_forwards()
     except BaseException:
         if sink is not None:
             sink.abandon()
