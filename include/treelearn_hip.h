@@ -452,6 +452,10 @@ int tl_cell_keys(const double* xyz, int64_t n, double cell, double min_bound, co
 int64_t tl_downsample_ws_words(int64_t n);
 int tl_downsample_reduce(const double* xyz, const int64_t* sorted_keys, const int64_t* perm, int64_t n, float* out_xyz,
                          int64_t* first_idx, int64_t* point2vox, int64_t* n_voxels, int32_t* ws, tl_stream_t stream);
+/* tl_downsample_reduce_r64: the same, but the double mean is rounded to 2 decimals in double and then cast to float32, the
+ *   order of the training-data generator (np.round(data, 2).astype(np.float32), tools/data_gen/gen_train_data.py:40-42). */
+int tl_downsample_reduce_r64(const double* xyz, const int64_t* sorted_keys, const int64_t* perm, int64_t n, float* out_xyz,
+                             int64_t* first_idx, int64_t* point2vox, int64_t* n_voxels, int32_t* ws, tl_stream_t stream);
 /* Group means for `ensemble` (tree_learn/util/pipeline.py:113-141: pandas groupby(['x','y','z']).mean() over the rounded
  * coordinates): keys sorted ascending with the stable permutation `perm`; per group and column the double-precision sum of
  * the members in input order divided by their number.  src f32[n,C]; mean f64[n,C] capacity (first n_groups rows written);
@@ -460,6 +464,40 @@ int tl_group_mean(const float* src, int64_t n, int C, const int64_t* sorted_keys
                   int64_t* first_idx, int64_t* n_groups, int32_t* ws, tl_stream_t stream);
 int tl_verticality(const double* xyz_sorted, const int64_t* sorted_keys, int64_t n, double radius, const int64_t* extent2,
                    float* out, tl_stream_t stream);
+
+/* ------------------------------------------------------------------ random training crops
+ * The random-crop half of SampleGenerator (tree_learn/util/data_preparation.py:136-330) on a plot resident in HBM; the
+ * grid and candidate lay-out stay on the host (util/crops.py).  f64 wherever the reference is f64, no fma contraction.
+ *
+ * tl_crops_occupancy <- get_occupancy_grid (data_preparation.py:154-166): xy f32[n,2] = the subsampled valid points;
+ *   x_steps f64[x_dim+1], y_steps f64[y_dim+1] ascending; grid u8[x_dim,y_dim] out = 1 where some point has
+ *   steps[i] < x <= steps[i+1] in x and in y (lower-bound search, exact f64 compare of the widened f32).
+ * tl_crops_fill <- fill_holes (data_preparation.py:571-586): an empty cell of `raw` becomes 1 when the occupied cells of the
+ *   window of +-how_far_fill cells, clipped at the borders, make count / (h*w) >= min_percent_occupied_fill (f64);
+ *   occupied cells stay 1.  filled u8[x_dim,y_dim] out, distinct from raw.
+ * tl_crops_check <- check_occupancy (data_preparation.py:209-230): one workgroup per candidate; cell (i, j) has the centre
+ *   (cell_x[i], cell_y[j]) f64 and is kept when max(|u|, |v|) <= chunk_size / 2 for (u, v) = (c - centre) @ Rinv.T, the
+ *   centre f32[k,2] widened, rinv f64[k,2,2] row-major.  sums f64[k] = sum of the kept cells' occupancy; pass u8[k] =
+ *   sums / denominator > min_percent_occupied_choose.  Either output may be null, not both.
+ * tl_crops_count / tl_crops_extract <- save (data_preparation.py:264-289), for a batch of 1..32 crops per plot read:
+ *   xyz f32[n,3], label f32[n], feat f32[n,F] the plot; a row belongs to crop c when max(|u|, |v|) <= chunk_size / 2 for
+ *   (u, v) = f64(xy - centre_c, a float32 subtraction) @ Rinv_c.T.  tl_crops_count writes counts i32[n_crops] (device) and
+ *   the row offsets into ws i32[tl_crops_ws_words(n, n_crops)]; tl_crops_extract then writes the crops one after another,
+ *   each in plot row order: out_xyz f32[.,3] = (f32 u, f32 v, z), out_label i32 (truncated label), out_feat f32[.,F];
+ *   rows at or beyond `capacity` are not written.  Offsets are int32: n * n_crops must stay below 2^31 (else TL_ERR_ARG). */
+int tl_crops_occupancy(const float* xy, int64_t n, const double* x_steps, int x_dim, const double* y_steps, int y_dim, uint8_t* grid,
+                       tl_stream_t stream);
+int tl_crops_fill(const uint8_t* raw, int x_dim, int y_dim, int how_far_fill, double min_percent_occupied_fill, uint8_t* filled,
+                  tl_stream_t stream);
+int tl_crops_check(const double* cell_x, int x_dim, const double* cell_y, int y_dim, const uint8_t* occupancy, const float* centres,
+                   const double* rinv, int64_t n_candidates, double chunk_size, double denominator, double min_percent_occupied_choose,
+                   double* sums, uint8_t* pass, tl_stream_t stream);
+int64_t tl_crops_ws_words(int64_t n, int n_crops);
+int tl_crops_count(const float* xyz, int64_t n, int n_crops, const float* centres, const double* rinv, double chunk_size, int32_t* counts,
+                   int32_t* ws, tl_stream_t stream);
+int tl_crops_extract(const float* xyz, const float* label, const float* feat, int64_t n, int F, int n_crops, const float* centres,
+                     const double* rinv, double chunk_size, const int32_t* ws, int64_t capacity, float* out_xyz, int32_t* out_label,
+                     float* out_feat, tl_stream_t stream);
 
 /* ------------------------------------------------------------------ clustering
  * Replaces sklearn DBSCAN(eps, min_samples=2) in group_dbscan (tree_learn/util/pipeline.py:173-180):

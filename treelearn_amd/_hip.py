@@ -157,6 +157,7 @@ PROTOTYPES = {
     "tl_cell_keys": (_i32, [_vp, _i64, _c.c_double, _c.c_double, _vp, _i32, _vp, _vp, _vp]),
     "tl_downsample_ws_words": (_i64, [_i64]),
     "tl_downsample_reduce": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tl_downsample_reduce_r64": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tl_group_mean": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tl_verticality": (_i32, [_vp, _vp, _i64, _c.c_double, _vp, _vp, _vp]),
     "tl_cluster_ws_bytes": (_i64, [_i64]),
@@ -176,6 +177,12 @@ PROTOTYPES = {
     "tl_eval_partition": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "tl_ring_lists": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tl_ring_covered": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "tl_crops_occupancy": (_i32, [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
+    "tl_crops_fill": (_i32, [_vp, _i32, _i32, _i32, _c.c_double, _vp, _vp]),
+    "tl_crops_check": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _c.c_double, _c.c_double, _c.c_double, _vp, _vp, _vp]),
+    "tl_crops_ws_words": (_i64, [_i64, _i32]),
+    "tl_crops_count": (_i32, [_vp, _i64, _i32, _vp, _vp, _c.c_double, _vp, _vp, _vp]),
+    "tl_crops_extract": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _c.c_double, _vp, _i64, _vp, _vp, _vp, _vp]),
     "tl_ring_classify": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 TL_EVAL_XY, TL_EVAL_Z = 0, 1

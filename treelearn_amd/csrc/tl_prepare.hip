@@ -73,6 +73,7 @@ __global__ void __launch_bounds__(256) k_head_scan(int32_t* __restrict__ part, i
   if (threadIdx.x == 0) *count = (int64_t)carry;
 }
 // one thread per voxel (segment of equal keys): in-order double sum, first index, trace
+template <bool kRoundF64>
 __global__ void __launch_bounds__(256) k_ds_reduce(const double* __restrict__ xyz, const int64_t* __restrict__ keys, const int64_t* __restrict__ perm,
                                                    int64_t n, const int32_t* __restrict__ part, float* __restrict__ out_xyz,
                                                    int64_t* __restrict__ first_idx, int64_t* __restrict__ point2vox) {
@@ -90,9 +91,14 @@ __global__ void __launch_bounds__(256) k_ds_reduce(const double* __restrict__ xy
         point2vox[o] = vox; ++cnt;
       }
       const double inv = (double)cnt;
-      // average in double (open3d), then .astype(float32) and np.round(., 2) in float32 (util/pipeline.py:44-45)
-      const float fx = (float)(sx / inv), fy = (float)(sy / inv), fz = (float)(sz / inv);
-      out_xyz[vox * 3] = rintf(fx * 100.0f) / 100.0f; out_xyz[vox * 3 + 1] = rintf(fy * 100.0f) / 100.0f; out_xyz[vox * 3 + 2] = rintf(fz * 100.0f) / 100.0f;
+      if (kRoundF64) {
+        // average in double (open3d), np.round(., 2) in double, then .astype(float32) (tools/data_gen/gen_train_data.py:40-42)
+        out_xyz[vox * 3] = (float)round2(sx / inv); out_xyz[vox * 3 + 1] = (float)round2(sy / inv); out_xyz[vox * 3 + 2] = (float)round2(sz / inv);
+      } else {
+        // average in double (open3d), then .astype(float32) and np.round(., 2) in float32 (util/pipeline.py:44-45)
+        const float fx = (float)(sx / inv), fy = (float)(sy / inv), fz = (float)(sz / inv);
+        out_xyz[vox * 3] = rintf(fx * 100.0f) / 100.0f; out_xyz[vox * 3 + 1] = rintf(fy * 100.0f) / 100.0f; out_xyz[vox * 3 + 2] = rintf(fz * 100.0f) / 100.0f;
+      }
       first_idx[vox] = perm[i];
       ++vox;
     }
@@ -203,16 +209,27 @@ int tl_cell_keys(const double* xyz, int64_t n, double cell, double min_bound, co
 
 int64_t tl_downsample_ws_words(int64_t n) { return tl_cdiv(n, kTile) + 1; }
 
-int tl_downsample_reduce(const double* xyz, const int64_t* sorted_keys, const int64_t* perm, int64_t n, float* out_xyz, int64_t* first_idx,
-                         int64_t* point2vox, int64_t* n_voxels, int32_t* ws, tl_stream_t stream) {
+static int downsample_reduce(bool round_f64, const double* xyz, const int64_t* sorted_keys, const int64_t* perm, int64_t n, float* out_xyz,
+                             int64_t* first_idx, int64_t* point2vox, int64_t* n_voxels, int32_t* ws, tl_stream_t stream) {
   if (!xyz || !sorted_keys || !perm || !out_xyz || !first_idx || !point2vox || !n_voxels || !ws || n <= 0) return TL_ERR_ARG;
   const int64_t nb = tl_cdiv(n, kTile);
   hipStream_t s = tl_s(stream);
   k_head_partials<<<(unsigned)nb, 256, 0, s>>>(sorted_keys, n, ws);
   k_head_scan<<<1, 256, 0, s>>>(ws, nb, n_voxels);
-  k_ds_reduce<<<(unsigned)nb, 256, 0, s>>>(xyz, sorted_keys, perm, n, ws, out_xyz, first_idx, point2vox);
+  if (round_f64) k_ds_reduce<true><<<(unsigned)nb, 256, 0, s>>>(xyz, sorted_keys, perm, n, ws, out_xyz, first_idx, point2vox);
+  else k_ds_reduce<false><<<(unsigned)nb, 256, 0, s>>>(xyz, sorted_keys, perm, n, ws, out_xyz, first_idx, point2vox);
   TL_CHECK_LAUNCH();
   return TL_OK;
+}
+
+int tl_downsample_reduce(const double* xyz, const int64_t* sorted_keys, const int64_t* perm, int64_t n, float* out_xyz, int64_t* first_idx,
+                         int64_t* point2vox, int64_t* n_voxels, int32_t* ws, tl_stream_t stream) {
+  return downsample_reduce(false, xyz, sorted_keys, perm, n, out_xyz, first_idx, point2vox, n_voxels, ws, stream);
+}
+
+int tl_downsample_reduce_r64(const double* xyz, const int64_t* sorted_keys, const int64_t* perm, int64_t n, float* out_xyz, int64_t* first_idx,
+                             int64_t* point2vox, int64_t* n_voxels, int32_t* ws, tl_stream_t stream) {
+  return downsample_reduce(true, xyz, sorted_keys, perm, n, out_xyz, first_idx, point2vox, n_voxels, ws, stream);
 }
 
 int tl_group_mean(const float* src, int64_t n, int C, const int64_t* sorted_keys, const int64_t* perm, double* mean, int64_t* first_idx,

@@ -42,10 +42,12 @@ def _keys(xyz, cell, origin, round_input):
     return keys, [t - b for t, b in zip(top, base)]
 
 
-def voxelize(data, voxel_size):
+def voxelize(data, voxel_size, round_first=False):
     """data [N, 3 (+ other columns)] -> (down-sampled [M, 3 (+ other)] float64 like the reference's np.hstack, trace).
     Coordinates: mean of the 2-decimal-rounded points of each voxel (in input order, double), then float32 and rounded to
-    2 decimals as `generate_tiles` does (util/pipeline.py:44-45); other columns: those of the first point of the voxel.
+    2 decimals as `generate_tiles` does (util/pipeline.py:44-45); with `round_first`, rounded to 2 decimals in double and
+    then float32, as the training-data generator does (tools/data_gen/gen_train_data.py:40-42).  Other columns: those of
+    the first point of the voxel.
     `trace` = dict(first_idx i64[M], point2vox i64[N]) on the device (the reference returns open3d's per-voxel index lists)."""
     L = _hip.lib()
     arr = data if torch.is_tensor(data) else torch.from_numpy(np.ascontiguousarray(data))
@@ -59,8 +61,9 @@ def voxelize(data, voxel_size):
     first = torch.empty(n, dtype=torch.int64, device=xyz.device); p2v = torch.empty(n, dtype=torch.int64, device=xyz.device)
     m = torch.empty(1, dtype=torch.int64, device=xyz.device)
     ws = torch.empty(int(L.tl_downsample_ws_words(n)), dtype=torch.int32, device=xyz.device)
-    _hip.check(L.tl_downsample_reduce(_hip.ptr(xyz), _hip.ptr(skeys), _hip.ptr(perm), n, _hip.ptr(out), _hip.ptr(first), _hip.ptr(p2v), _hip.ptr(m),
-                                      _hip.ptr(ws), _hip.stream()), "tl_downsample_reduce")
+    fn = L.tl_downsample_reduce_r64 if round_first else L.tl_downsample_reduce
+    _hip.check(fn(_hip.ptr(xyz), _hip.ptr(skeys), _hip.ptr(perm), n, _hip.ptr(out), _hip.ptr(first), _hip.ptr(p2v), _hip.ptr(m),
+                  _hip.ptr(ws), _hip.stream()), "tl_downsample_reduce")
     M = int(m.item())
     pts = out[:M]; first = first[:M]
     if arr.shape[1] > 3:
