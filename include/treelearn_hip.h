@@ -589,6 +589,24 @@ int tl_eval_partition(const double* xyz, const int64_t* gt, const int64_t* pred,
                       int64_t n_gt, const int64_t* pred_order, const int64_t* pred_start, int64_t n_pred, const int64_t* pairs, int64_t m,
                       const double* edges, int n_edges, int mode, int64_t* tp, int64_t* fp, int64_t* fn, double* norm, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ validation metrics of a training run (csrc/tl_train_eval.hip)
+ * Replaces `pointwise_eval` (tools/training/train.py:89-102) and the per-tile lists `validate` (:61-86) concatenates for it: called once
+ * per validation tile, it ADDS that tile's share to a running state and keeps nothing per point.
+ *   logits [n,2], offsets [n,3]: f32 / bf16 / f16 by `dtype` (TL_F32 / TL_BF16 / TL_F16), widened to fp32 on load (the reference's .float());
+ *   semantic_labels i64[n]; offset_labels f32[n,3]; mask u8[n] (rows with mask != 0 count; NULL = every row): `masks_sem` of the tile.
+ *   Per counted row, in fp32: pred = softmax(logits)[0] >= 0.5 (tree class 0, ties count as tree), tree = semantic_labels == 0;
+ *   tp / fp / tn / fn as get_eval_components defines them; for tree rows sum_off += (double) sqrt(sum((offset - offset_label)^2)), n_off += 1
+ *   (masks_off = semantic_labels == TREE_CLASS and nothing else, train.py:92).
+ *   state: 64 bytes, 8-byte aligned = int64 tp, fp, tn, fn, n_off; float64 sum_off; two reserved words.  Zeroed by the caller before the
+ *   first tile, read back once after the last: acc = (tp + tn) / (tp + fp + tn + fn), Offset_MAE = sum_off / n_off.
+ *   ws: tl_pointwise_eval_ws_bytes(n) bytes of per-workgroup partials.  Two stages (workgroup partials, then one workgroup that sums them
+ *   in index order), integer counts and a float64 sum, no float atomics: the state is bit-reproducible from run to run.
+ *   n = 0 is a no-op.  Arrays that are 16-byte aligned are read with 16-byte loads, four rows per lane; any other alignment of whole
+ *   elements is served row by row. */
+int64_t tl_pointwise_eval_ws_bytes(int64_t n);
+int tl_pointwise_eval(const void* logits, const void* offsets, int dtype, const int64_t* semantic_labels, const float* offset_labels,
+                      const uint8_t* mask, int64_t n, void* state, void* ws, tl_stream_t stream);
+
 /* ------------------------------------------------------------------ points against the plot outline (csrc/tl_hull.hip)
  * Replaces `get_coords_within_shape` (tree_learn/util/pipeline.py:211-223: a shapely Point per point + a geopandas sjoin) on the
  * polygon of `get_hull` (:256-265) and on the ring buffer of `get_hull_buffer` (:240-253), as tools/pipeline/pipeline.py:80-81,136-142,

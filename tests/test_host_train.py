@@ -1,0 +1,190 @@
+"""Host side of the training program (no GPU): LR schedule, checkpoints, config merge, the two new C entries, ScalarLog, both CLIs,
+and the CPU restatement the GPU tests lean on."""
+import ctypes
+import json
+import math
+import os
+import re
+
+import pytest
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _opt(lr=3e-3):
+    return torch.optim.AdamW([torch.nn.Parameter(torch.zeros(3))], lr=lr, weight_decay=1e-3)
+
+
+def test_cosine_schedule_closed_forms():
+    """timm 0.6.12's CosineLRScheduler for the reference's arguments, against closed forms in float64 (1e-12 relative)."""
+    from treelearn_amd.util.train import build_cosine_scheduler
+    base, lr_min, w0 = 3e-3, 5e-5, 1e-5
+    cfg = dict(t_initial=1000, lr_min=lr_min, cycle_decay=1, warmup_lr_init=w0, warmup_t=50, cycle_limit=1, t_in_epochs=True)   # configs/training/train.yaml
+    opt = _opt(base)
+    sch = build_cosine_scheduler(cfg, opt)
+    lr = lambda: opt.param_groups[0]["lr"]                                               # noqa: E731
+    assert lr() == w0                                                                    # set at construction
+    sch.step(0); assert lr() == pytest.approx(w0, rel=1e-12)
+    sch.step(1); assert lr() == pytest.approx(w0 + (base - w0) / 50, rel=1e-12)
+    sch.step(49); assert lr() == pytest.approx(w0 + 49 * (base - w0) / 50, rel=1e-12)
+    sch.step(50); assert lr() == pytest.approx(lr_min + 0.5 * (base - lr_min) * (1 + math.cos(0.05 * math.pi)), rel=1e-12)
+    sch.step(500); assert lr() == pytest.approx((base + lr_min) / 2, rel=1e-12)
+    for t in (1000, 1001, 2500):
+        sch.step(t); assert lr() == pytest.approx(lr_min, rel=1e-12)
+    # attribute-style config, two cycles with decay
+    from treelearn_amd.util.config import Config
+    cfg2 = Config(t_initial=100, lr_min=lr_min, cycle_decay=0.5, warmup_lr_init=w0, warmup_t=0, cycle_limit=2, t_in_epochs=True)
+    opt = _opt(base)
+    sch = build_cosine_scheduler(cfg2, opt)
+    assert lr() == base                                                                  # no warmup: untouched at construction
+    sch.step(0); assert lr() == pytest.approx(base, rel=1e-12)
+    sch.step(100); assert lr() == pytest.approx(base * 0.5, rel=1e-12)                    # the second cycle's peak
+    sch.step(150); assert lr() == pytest.approx(lr_min + 0.5 * (base * 0.5 - lr_min), rel=1e-12)
+    for t in (200, 201, 1000):
+        sch.step(t); assert lr() == pytest.approx(lr_min, rel=1e-12)
+    # a schedule that counts updates ignores step(epoch)
+    opt = _opt(base)
+    sch = build_cosine_scheduler(dict(cfg, t_in_epochs=False), opt)
+    sch.step(500); assert lr() == w0
+    sch.step_update(500); assert lr() == pytest.approx((base + lr_min) / 2, rel=1e-12)
+
+
+def test_checkpoint_save_retention_and_round_trip(tmp_path):
+    from treelearn_amd.model import TreeLearn
+    from treelearn_amd.util.train import build_optimizer, checkpoint_save, is_multiple, load_checkpoint, weights_to_cpu
+    assert is_multiple(4, 2) and not is_multiple(0, 2) and not is_multiple(5, 2)
+    cfg = dict(channels=16, num_blocks=2, use_feats=False, use_coords=False, spatial_shape=[64, 64, 64])
+    torch.manual_seed(0)
+    model = TreeLearn(**cfg)
+    opt = build_optimizer(model, dict(type="AdamW", lr=1e-3, weight_decay=1e-3))
+    assert isinstance(opt, torch.optim.AdamW) and opt.param_groups[0]["weight_decay"] == 1e-3
+    for p in model.parameters():
+        p.grad = torch.randn_like(p)
+    opt.step()
+    work = str(tmp_path)
+    for epoch in range(1, 6):
+        checkpoint_save(epoch, model, opt, work, save_freq=2)
+    assert sorted(os.listdir(work)) == ["epoch_2.pth", "epoch_4.pth", "epoch_5.pth"]
+    state = torch.load(os.path.join(work, "epoch_4.pth"), map_location="cpu")
+    assert set(state) == {"net", "optimizer", "epoch"} and state["epoch"] == 4
+    assert all(v.device.type == "cpu" for v in state["net"].values())
+    assert all(v.device.type == "cpu" for v in weights_to_cpu(model.state_dict()).values())
+    torch.manual_seed(1)
+    fresh = TreeLearn(**cfg)
+    opt2 = build_optimizer(fresh, dict(type="AdamW", lr=1e-3, weight_decay=1e-3))
+    assert load_checkpoint(os.path.join(work, "epoch_4.pth"), None, fresh, optimizer=opt2) == 5
+    a, b = model.state_dict(), fresh.state_dict()
+    assert list(a) == list(b) and all(torch.equal(a[k], b[k]) for k in a)
+    sa, sb = opt.state_dict(), opt2.state_dict()
+    assert sa["param_groups"] == sb["param_groups"] and list(sa["state"]) == list(sb["state"])
+    for k in sa["state"]:
+        for name, v in sa["state"][k].items():
+            assert torch.equal(torch.as_tensor(v), torch.as_tensor(sb["state"][k][name])), (k, name)
+
+
+def test_config_merge_and_path_resolution(tmp_path, monkeypatch):
+    from treelearn_amd.util.config import Config, get_config, to_dict
+    root = tmp_path / "proj"
+    (root / "configs" / "_modular").mkdir(parents=True)
+    (root / "configs" / "training").mkdir(parents=True)
+    (root / "configs" / "_modular" / "model.yaml").write_text("model:\n  channels: 32\n  num_blocks: 7\n  spatial_shape: ~\n  nested:\n    a: 1\n    b: 2\n")
+    (root / "configs" / "_modular" / "data.yaml").write_text("dataset_train:\n  training: True\n  data_root: 'x/y'\n  data_augmentations:\n    jitter: True\n    flip: True\n")
+    main = root / "configs" / "training" / "train.yaml"
+    main.write_text('default_args: ["configs/_modular/model.yaml", "configs/_modular/data.yaml"]\n'
+                    "model:\n  spatial_shape: [500, 500, 1000]\n  nested:\n    b: 3\n"
+                    "dataset_train:\n  data_augmentations:\n    flip: False\n"
+                    "optimizer:\n  type: 'AdamW'\n  lr: 0.003\nepochs: 5\npretrain: ~\n")
+    monkeypatch.chdir(tmp_path)                                   # the default_args paths do not exist relative to here: ancestor fallback
+    cfg = get_config(str(main))
+    assert "default_args" not in cfg
+    assert cfg.model.spatial_shape == [500, 500, 1000] and cfg.model.channels == 32 and cfg.model.num_blocks == 7
+    assert cfg.model.nested == {"a": 1, "b": 3}
+    assert cfg.dataset_train.data_augmentations.flip is False and cfg.dataset_train.data_augmentations.jitter is True
+    assert cfg.dataset_train.data_root == "x/y" and cfg.optimizer.lr == 0.003 and cfg.epochs == 5 and cfg.pretrain is None
+    assert isinstance(cfg, Config) and isinstance(cfg.model, Config) and cfg["model"]["channels"] == 32
+    cfg.work_dir = "w"
+    assert cfg["work_dir"] == "w"
+    with pytest.raises(AttributeError):
+        cfg.no_such_key
+    plain = to_dict(cfg)
+    assert type(plain) is dict and type(plain["model"]) is dict
+    monkeypatch.chdir(root)                                       # as given, the reference's way
+    assert to_dict(get_config(str(main))) == {k: v for k, v in plain.items() if k != "work_dir"}
+    (root / "configs" / "training" / "bad.yaml").write_text('default_args: ["configs/_modular/none.yaml"]\n')
+    with pytest.raises(FileNotFoundError):
+        get_config(str(root / "configs" / "training" / "bad.yaml"))
+
+
+def test_new_entry_points_are_declared_prototyped_and_exported():
+    from treelearn_amd import _hip, build as b
+    hdr = open(os.path.join(REPO, "include", "treelearn_hip.h")).read()
+    names = set(re.findall(r"\b(tl_[a-z0-9_]+)\s*\(", hdr))
+    L = ctypes.CDLL(b.build(verbose=False))
+    for n in ("tl_pointwise_eval", "tl_pointwise_eval_ws_bytes"):
+        assert n in names and n in _hip.PROTOTYPES and hasattr(L, n)
+    assert "train.py:89-102" in hdr
+    lib = _hip.lib()
+    assert lib.tl_pointwise_eval_ws_bytes(0) >= 64 and lib.tl_pointwise_eval_ws_bytes(1 << 22) >= lib.tl_pointwise_eval_ws_bytes(1000)
+    assert lib.tl_pointwise_eval_ws_bytes(1 << 40) == lib.tl_pointwise_eval_ws_bytes(1 << 30)      # bounded: the grid is capped
+    # null pointers, a negative count, an unknown dtype: refused before anything is launched (no GPU here)
+    buf = (ctypes.c_int64 * 64)()
+    p = ctypes.addressof(buf)
+    assert lib.tl_pointwise_eval(None, None, 0, None, None, None, 0, None, None, None) < 0
+    assert lib.tl_pointwise_eval(p, p, 0, p, p, None, -1, p, p, None) < 0
+    assert lib.tl_pointwise_eval(p, p, 7, p, p, None, 4, p, p, None) < 0
+    assert lib.tl_pointwise_eval(p, p, 0, p, p, None, 4, p + 4, p, None) < 0                        # misaligned state
+    assert lib.tl_pointwise_eval(p, p, 0, p, p, None, 0, p, p, None) == 0                           # n == 0: a no-op
+
+
+def test_scalar_log_round_trips(tmp_path):
+    from treelearn_amd.util.trainer import ScalarLog
+    w = ScalarLog(str(tmp_path / "run"))
+    w.add_scalar("train/learning_rate", 3e-3, 1)
+    w.add_scalar("val/acc", torch.tensor(0.75), 1)
+    w.add_scalar("val/Offset_MAE", 1.25, 2)
+    w.flush()
+    lines = [json.loads(s) for s in open(tmp_path / "run" / "scalars.jsonl").read().splitlines()]
+    assert lines == [dict(tag="train/learning_rate", value=3e-3, step=1), dict(tag="val/acc", value=0.75, step=1),
+                     dict(tag="val/Offset_MAE", value=1.25, step=2)]
+    w.close()
+    w2 = ScalarLog(str(tmp_path / "run"))                        # a resumed run appends
+    w2.add_scalar("val/acc", 0.5, 3); w2.close()
+    assert [r["step"] for r in ScalarLog.read(w2.path)] == [1, 1, 2, 3]
+
+
+def test_command_lines_accept_the_documented_flags():
+    from treelearn_amd.util import tiles, trainer
+    a = trainer.parse_args(["--config", "configs/training/train.yaml", "--resume", "work_dirs/x/epoch_40.pth", "--work_dir", "run7"])
+    assert (a.config, a.resume, a.work_dir) == ("configs/training/train.yaml", "work_dirs/x/epoch_40.pth", "run7")
+    assert trainer.work_dir_of(a) == os.path.join("./work_dirs", "run7")
+    b = trainer.parse_args(["--config", "a/b/train_small.yaml"])
+    assert b.resume is None and trainer.work_dir_of(b) == os.path.join("./work_dirs", "train_small")
+    with pytest.raises(SystemExit):
+        trainer.parse_args([])
+    t = tiles.parse_args(["--forest", "data/val/forest/L1W.npy"])
+    assert t.forest == "data/val/forest/L1W.npy" and (t.voxel_size, t.inner_edge, t.outer_edge, t.stride) == (0.1, 8, 13.5, 1)
+    t = tiles.parse_args(["--forest", "f.npz", "--voxel-size", "0.2", "--inner-edge", "6", "--outer-edge", "9", "--stride", "0.5"])
+    assert (t.voxel_size, t.inner_edge, t.outer_edge, t.stride) == (0.2, 6.0, 9.0, 0.5)
+    with pytest.raises(SystemExit):
+        tiles.parse_args(["--forest", "f.npz", "--stride", "0"])
+
+
+def test_write_tiles_refuses_the_denoising_keys(tmp_path):
+    from treelearn_amd.util.tiles import write_tiles
+    for k in ("n_neigh_sor", "multiplier_sor", "rad", "npoints_rad"):
+        with pytest.raises(NotImplementedError, match=k):
+            write_tiles(str(tmp_path / "forest" / "p.npy"), dict(sample_generator={k: 2.0}))
+
+
+def test_restatement_on_a_hand_worked_example():
+    import train_restatement as R
+    logits = torch.tensor([[2.0, 0.0], [0.0, 2.0], [1.0, 1.0], [0.0, 3.0], [5.0, 1.0]])        # tree, non-tree, tie (tree), non-tree, tree
+    sem = torch.tensor([0, 0, 1, 1, 0])
+    off = torch.tensor([[3.0, 4.0, 0.0], [0.0, 0.0, 0.0], [9.0, 9.0, 9.0], [1.0, 1.0, 1.0], [1.0, 2.0, 2.0]])
+    lab = torch.zeros(5, 3)
+    r = R.pointwise_eval(logits, off, sem, lab)
+    assert (r["tp"], r["fp"], r["tn"], r["fn"], r["n_off"]) == (2, 1, 1, 1, 3)
+    assert r["acc"] == pytest.approx(0.6) and r["offset_mae"] == pytest.approx((5.0 + 0.0 + 3.0) / 3)
+    r = R.pointwise_eval(logits, off, torch.ones(5, dtype=torch.long), lab)
+    assert r["n_off"] == 0 and r["offset_mae"] == 0.0

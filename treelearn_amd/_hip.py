@@ -175,6 +175,8 @@ PROTOTYPES = {
     "tl_knn_vote_grid": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _c.c_float * 3, _f32, _I3, _vp, _i64, _i32, _vp, _vp]),
     "tl_eval_contingency": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "tl_eval_partition": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "tl_pointwise_eval_ws_bytes": (_i64, [_i64]),
+    "tl_pointwise_eval": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "tl_ring_lists": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tl_ring_covered": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "tl_crops_occupancy": (_i32, [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),

@@ -1,4 +1,5 @@
-from .train import cuda_cast, point_wise_loss, load_checkpoint  # noqa: F401
+from .train import (cuda_cast, point_wise_loss, load_checkpoint, checkpoint_save, is_multiple, weights_to_cpu, build_optimizer,  # noqa: F401
+                    build_cosine_scheduler, build_dataloader)
 from .pipeline import get_pointwise_preds, get_instances, group_dbscan, make_labels_consecutive  # noqa: F401
 from .postprocess import propagate_preds  # noqa: F401
 from .eval import (get_detections, get_detection_failures, evaluate_instance_segmentation, evaluate_no_partition,  # noqa: F401

@@ -14,8 +14,18 @@ among the ten lowest points -- and on float32 summation order, so for bit-identi
 host from the cropped tile exactly as the reference's DataLoader worker does (`offset_labels="host"`, the default).
 Pure inference does not use them (`get_instances` reads coordinates, logits, offsets and the verticality
 feature only): `offset_labels="none"` skips the D2H copy and returns zeros / an all-false `masks_off`.
+
+`write_tiles` is the file form of the same chain, the reference's `generate_tiles` as tools/data_gen/gen_val_data.py calls it for
+the validation forest of a training run:
+
+    python -m treelearn_amd.util.tiles --forest PATH [--voxel-size V] [--inner-edge I] [--outer-edge O] [--stride S]
 """
+import argparse
 import ctypes
+import json
+import os
+import os.path as osp
+import sys
 
 import numpy as np
 import torch
@@ -154,3 +164,107 @@ class PlotTiler:
                 v.record_stream(main)                      # allocated on the tiler's stream, consumed on the caller's
         batch["_ready_event"] = ready                      # consumers on another stream wait for this before reading the tile
         return batch
+
+
+# ------------------------------------------------------------------------------------------------ validation tiles on disk
+# configs/data_gen/gen_val_data.yaml over configs/_modular/sample_generation.yaml of the reference (stride 1: tiles do not overlap)
+VAL_CFG = dict(voxel_size=0.1, search_radius_features=0.6, inner_edge=8, outer_edge=13.5, stride=1,
+               sample_generator=dict(n_neigh_sor=None, multiplier_sor=None, rad=None, npoints_rad=None))
+_FILTER_KEYS = ("n_neigh_sor", "multiplier_sor", "rad", "npoints_rad")
+
+
+def write_tiles(forest_path, sample_cfg=None, logger=None):
+    """`generate_tiles` (tree_learn/util/pipeline.py:24-75) + `tile_generate_and_save` (data_preparation.py:333-494, plot_corners=None) for
+    a labelled forest <base>/<dir>/<plot>.<ext>: writes <base>/forest_voxelized<v>/<plot>.npz (points, labels) and
+    <base>/features/<plot>.npz (features) unless they exist -- the cache files util/crops.py writes for training forests -- then one
+    <base>/tiles/npz/<plot>_<i>.npz (points f32 centred on the tile, feat f32, instance_label i32, center f64[3]) and
+    <base>/tiles/json/<plot>_<i>.json per tile whose inner square holds a point, i counting those tiles.  `CropDataset(<base>/tiles/npz,
+    inner_square_edge_length, training=False)` reads them.  Returns the number of tiles written."""
+    from .prepare import compute_features, voxelize
+    from .segment import load_forest
+    cfg = dict(VAL_CFG, **{k: v for k, v in dict(sample_cfg or {}).items()})
+    gen = dict(VAL_CFG["sample_generator"], **dict(cfg.get("sample_generator") or {}))
+    for k in _FILTER_KEYS:
+        if gen.get(k) is not None:
+            raise NotImplementedError(f"{k} is set: open3d's outlier filters are not part of this project "
+                                      "(sample_generation.yaml leaves them off)")
+    say = (lambda m: logger.info(m)) if logger is not None else (lambda m: None)
+    plot_name = osp.basename(forest_path)[:-4]
+    base_dir = osp.dirname(osp.dirname(osp.abspath(forest_path)))
+    voxelized_dir = osp.join(base_dir, f"forest_voxelized{cfg['voxel_size']}")
+    features_dir = osp.join(base_dir, "features")
+    save_dir = osp.join(base_dir, "tiles")
+    for d in (voxelized_dir, features_dir, osp.join(save_dir, "npz"), osp.join(save_dir, "json")):
+        os.makedirs(d, exist_ok=True)
+
+    say("voxelizing forest...")
+    path_vox = osp.join(voxelized_dir, f"{plot_name}.npz")
+    if not osp.exists(path_vox):
+        data = load_forest(forest_path)
+        if data.shape[1] == 3:                                                    # load_data: unlabelled clouds get -1
+            data = np.hstack([data, IGNORE_LABEL * np.ones(len(data))[:, np.newaxis]])
+        vox, _ = voxelize(data, cfg["voxel_size"])
+        vox = np.round(vox.cpu().numpy().astype(np.float32), 2)
+        np.savez_compressed(path_vox, points=vox[:, :3], labels=vox[:, 3])
+    say("calculating features...")
+    path_feat = osp.join(features_dir, f"{plot_name}.npz")
+    if not osp.exists(path_feat):
+        pts = np.load(path_vox)["points"]
+        feats = compute_features(pts.astype(np.float64), search_radius=cfg["search_radius_features"])
+        np.savez_compressed(path_feat, features=feats.cpu().numpy())
+
+    say("getting tiles...")
+    d = np.load(path_vox)
+    feats = np.load(path_feat)["features"]
+    tiler = PlotTiler(d["points"], d["labels"], feats)
+    inner, outer = tile_grid(tiler.x_range, tiler.y_range, cfg["inner_edge"], cfg["outer_edge"], cfg["stride"])
+    F = tiler.feats.shape[1]
+    meta = {"plot_name": plot_name, "n_neigh_sor": gen["n_neigh_sor"], "multiplier_sor": gen["multiplier_sor"], "rad": gen["rad"],
+            "npoints_rad": gen["npoints_rad"], "inner_edge": cfg["inner_edge"], "outer_edge": cfg["outer_edge"]}
+    i = 0
+    for t in range(len(inner)):
+        # the masks the crop also fills are not stored (the dataset derives them from the points), so their edge length does not matter here
+        kept, n_inner, center = tiler.crop(inner[t], outer[t], cfg["inner_edge"])
+        if n_inner == 0:
+            continue
+        b = tiler._buf
+        data = dict(points=b["coords"][:kept].cpu().numpy(), feat=b["feats"][:kept, :F].cpu().numpy(),
+                    instance_label=b["inst"][:kept].cpu().numpy().astype(np.int32), center=center)
+        np.savez(osp.join(save_dir, "npz", f"{plot_name}_{i}.npz"), **data)
+        with open(osp.join(save_dir, "json", f"{plot_name}_{i}.json"), "w") as f:
+            json.dump(meta, f)
+        i += 1
+    return i
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser("python -m treelearn_amd.util.tiles", description="write the validation tiles of a labelled forest")
+    ap.add_argument("--forest", required=True, help="labelled cloud <base>/<dir>/<plot>.npy|npz|txt, N x 4; tiles go to <base>/tiles")
+    ap.add_argument("--voxel-size", type=float, default=VAL_CFG["voxel_size"])
+    ap.add_argument("--search-radius-features", type=float, default=VAL_CFG["search_radius_features"])
+    ap.add_argument("--inner-edge", type=float, default=VAL_CFG["inner_edge"])
+    ap.add_argument("--outer-edge", type=float, default=VAL_CFG["outer_edge"])
+    ap.add_argument("--stride", type=float, default=VAL_CFG["stride"])
+    a = ap.parse_args(argv)
+    for k in ("voxel_size", "search_radius_features", "inner_edge", "outer_edge", "stride"):
+        if not getattr(a, k) > 0:
+            ap.error(f"--{k.replace('_', '-')} must be > 0")
+    return a
+
+
+def main(argv=None):
+    import logging
+    a = parse_args(argv)
+    if not osp.exists(a.forest):
+        print(f"--forest {a.forest}: no such file", file=sys.stderr)
+        return 2
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
+    cfg = dict(voxel_size=a.voxel_size, search_radius_features=a.search_radius_features, inner_edge=a.inner_edge, outer_edge=a.outer_edge,
+               stride=a.stride)
+    n = write_tiles(a.forest, cfg, logger=logging.getLogger("treelearn_amd.tiles"))
+    print(f"{n} tiles -> {osp.join(osp.dirname(osp.dirname(osp.abspath(a.forest))), 'tiles')}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
