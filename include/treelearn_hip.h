@@ -607,6 +607,43 @@ int64_t tl_pointwise_eval_ws_bytes(int64_t n);
 int tl_pointwise_eval(const void* logits, const void* offsets, int dtype, const int64_t* semantic_labels, const float* offset_labels,
                       const uint8_t* mask, int64_t n, void* state, void* ws, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ training / validation batches on the device (csrc/tl_train_batch.hip)
+ * Replaces the per-item numpy work of TreeDataset.__getitem__ (tree_learn/dataset/dataset.py:34-140) and the concatenation of
+ * collate_fn (:167-226) for crops and tiles whose rows are already in HBM.
+ *
+ * tl_point_jitter <- point_jitter (dataset.py:92-95), in place on xyz f32[n,3]: x <- f32(f64(x) + clip(0.1 g, -0.2, 0.2)).  g is a standard
+ *   normal from a counter-based generator (splitmix64 of (key, row, component) -> two uniforms -> Box-Muller in f64): a function of
+ *   (key, row, component) only, so the same key gives the same bits for any launch shape.  These are NOT numpy's draws: a run that
+ *   jitters is statistically, not bitwise, the reference's.
+ *
+ * tl_train_item <- dataset.py:41-66 (labels, centre, masks), :85-89 (the matrix of transform_train), :111-140 (offset labels), fused; ONE crop
+ *   or tile per call, written at rows [row_offset, row_offset + n) of batch-sized outputs, so collate_fn's concatenation is the offset.
+ *   xyz f32[n,3], instance_label i32[n] (device); m = HOST f64[9], row-major, or NULL for test mode; center = HOST f32[3], or NULL for the
+ *   training dummy of ones.  Outputs (device, batch bases): coords f32[.,3], semantic_labels i64 (label 0 -> 1, else 0), instance_labels
+ *   i64, offset_labels f32[.,3], masks_inner / masks_off / masks_sem u8, batch_ids i64 (= batch_id), centers f32[.,3].  Features are not
+ *   touched: they stay a plain copy.
+ *   Coordinate type: with m, c = x m[0][k] + y m[1][k] + z m[2][k] in f64 (no fma contraction), coords = f32(c), and every comparison and
+ *   the offset subtraction are f64 on c (np.matmul(xyz32, m64) makes the reference's training items float64); without m they are f32 on
+ *   the stored values and `low + 0.5` is rounded to f32 (the reference's test items stay float32).
+ *   Tree base, per distinct label != 0 (any int32 values, any number of them; -1 is an instance of its own here, masks_off removes it):
+ *   low = the 4th smallest z, RANK 3 WITH DUPLICATES COUNTED (np.sort(z)[3]), for an instance of more than 11 rows, its minimum otherwise.
+ *   The reference's np.partition(z, 10)[3] is an implementation-defined element among the ten lowest; the device rule is rank 3 by
+ *   definition.  position = f32(mean of the instance's rows with z <= low + 0.5); the sum is an exact INTEGER sum: every addend is
+ *   floor(c * 2^60) as a 128-bit two's-complement integer (split as trunc(c) + the exact remainder; off by less than 2^-60 per addend, for
+ *   every finite c including -0.0 and tiny negatives), added with integer atomics; coordinates must be finite and below 2^32 in magnitude.
+ *   The division is f64.  offset = f32(position - c); rows of label 0 get
+ *   position = 1.  masks_inner = max(|x|, |y|) <= half_inner; masks_sem = inner & (label != -1); masks_off = masks_sem & (label != 0)
+ *   (the reference's `valid` is always true for a tree instance: the row of rank 3 is a base row).
+ *   No floating-point atomics: two calls on the same input give identical bits, at any row_offset.
+ *   ws: tl_train_item_ws_bytes(n) bytes, 256-byte aligned (label table, per-row slot and z image, 128 B per possible instance).
+ *   n <= 0, n > 2^30, a null or misaligned pointer: TL_ERR_ARG, nothing launched (tl_train_item_ws_bytes returns 0 for such n). */
+int tl_point_jitter(float* xyz, int64_t n, uint64_t key, tl_stream_t stream);
+int64_t tl_train_item_ws_bytes(int64_t n);
+int tl_train_item(const float* xyz, const int32_t* instance_label, int64_t n, const double* m, double half_inner, const float* center,
+                  int64_t batch_id, int64_t row_offset, float* coords, int64_t* semantic_labels, int64_t* instance_labels,
+                  float* offset_labels, uint8_t* masks_inner, uint8_t* masks_off, uint8_t* masks_sem, int64_t* batch_ids, float* centers,
+                  void* ws, tl_stream_t stream);
+
 /* ------------------------------------------------------------------ points against the plot outline (csrc/tl_hull.hip)
  * Replaces `get_coords_within_shape` (tree_learn/util/pipeline.py:211-223: a shapely Point per point + a geopandas sjoin) on the
  * polygon of `get_hull` (:256-265) and on the ring buffer of `get_hull_buffer` (:240-253), as tools/pipeline/pipeline.py:80-81,136-142,

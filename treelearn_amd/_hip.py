@@ -177,6 +177,10 @@ PROTOTYPES = {
     "tl_eval_partition": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "tl_pointwise_eval_ws_bytes": (_i64, [_i64]),
     "tl_pointwise_eval": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "tl_point_jitter": (_i32, [_vp, _i64, _c.c_uint64, _vp]),
+    "tl_train_item_ws_bytes": (_i64, [_i64]),
+    "tl_train_item": (_i32, [_vp, _vp, _i64, _c.POINTER(_c.c_double), _c.c_double, _c.POINTER(_f32), _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp]),
     "tl_ring_lists": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tl_ring_covered": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "tl_crops_occupancy": (_i32, [_vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),

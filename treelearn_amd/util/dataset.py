@@ -71,10 +71,18 @@ class CropDataset(Dataset):
 
     def transform_train(self, xyz, rs, aug_prob=0.5, aug_prob_point_jitter=0.25):
         """dataset.py:92-103,143-164: point jitter in place on the float32 array, then one float64 matrix."""
+        if self.point_jitter_coin(rs, aug_prob_point_jitter):
+            xyz += np.clip(0.1 * rs.randn(xyz.shape[0], 3), -1 * 0.2, 0.2)
+        return np.matmul(xyz, self.augmentation_matrix(rs, aug_prob))
+
+    def point_jitter_coin(self, rs, aug_prob_point_jitter=0.25):
+        """dataset.py:92-93: whether this item is jittered (one draw, only when the augmentation is on)."""
+        return self.data_augmentations["point_jitter"] == True and rs.random() <= aug_prob_point_jitter      # noqa: E712  (the reference's test)
+
+    def augmentation_matrix(self, rs, aug_prob=0.5):
+        """dataset.py:143-164: the float64 3 x 3 matrix of one item, drawn in the reference's order.  Shared with the device path
+        (util/device_dataset.DeviceCropLoader), which hands it to tl_train_item instead of multiplying on the host."""
         aug = self.data_augmentations
-        if aug["point_jitter"] == True:                                            # noqa: E712  (the reference's test)
-            if rs.random() <= aug_prob_point_jitter:
-                xyz += np.clip(0.1 * rs.randn(xyz.shape[0], 3), -1 * 0.2, 0.2)
         m = np.eye(3)
         if aug["scaled"] and rs.rand() < aug_prob:
             scale_xy = rs.uniform(0.8, 1.2, 2)
@@ -87,7 +95,7 @@ class CropDataset(Dataset):
         if aug["rot"] and rs.rand() < aug_prob:
             theta = rs.rand() * 2 * math.pi
             m = np.matmul(m, [[math.cos(theta), math.sin(theta), 0], [-math.sin(theta), math.cos(theta), 0], [0, 0, 1]])
-        return np.matmul(xyz, m)
+        return m
 
     def collate_fn(self, batch):
         return collate(batch)

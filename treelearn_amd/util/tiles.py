@@ -12,6 +12,9 @@ square) and every dtype decision are the reference's (golden G11).
 Offset labels (dataset.py:111-140) depend on numpy's `np.partition(z, 10)[3]` -- an implementation-defined element
 among the ten lowest points -- and on float32 summation order, so for bit-identical labels they are derived on the
 host from the cropped tile exactly as the reference's DataLoader worker does (`offset_labels="host"`, the default).
+`offset_labels="device"` derives them on the device instead (tl_train_item in test mode): the tree base starts at the 4th
+smallest z by definition and is an exact sum, so the labels agree with the host's to float32 rounding wherever numpy's pick is that
+element, and nothing is copied to the host.
 Pure inference does not use them (`get_instances` reads coordinates, logits, offsets and the verticality
 feature only): `offset_labels="none"` skips the D2H copy and returns zeros / an all-false `masks_off`.
 
@@ -118,7 +121,7 @@ class PlotTiler:
 
     def tiles(self, inner_edge, outer_edge, stride, inner_square_edge_length, offset_labels="host"):
         """Generator of batch dicts (collate_fn's keys, batch size 1), in the reference's tile numbering."""
-        assert offset_labels in ("host", "none")
+        assert offset_labels in ("host", "none", "device")
         inner, outer = tile_grid(self.x_range, self.y_range, inner_edge, outer_edge, stride)
         F = self.feats.shape[1]
         main = torch.cuda.current_stream()
@@ -133,7 +136,7 @@ class PlotTiler:
         square holds no point (data_preparation.py:412-427).  Random access for callers that own only some tiles of a plot (a rank of the
         sharded tile loop) or lay the squares out themselves.  `sync_with_caller=False`: the caller has already made the tiler's stream wait
         for whatever produced the plot arrays (`tiles()` does so once) -- the crop then does not queue behind the caller's stream."""
-        assert offset_labels in ("host", "none")
+        assert offset_labels in ("host", "none", "device")
         F = self.feats.shape[1]
         main = torch.cuda.current_stream()
         if sync_with_caller:
@@ -146,6 +149,16 @@ class PlotTiler:
             if n_inner == 0:                               # data_preparation.py:412-427: tiles whose inner square is empty are dropped
                 return None
             b = self._buf
+            if offset_labels == "device":
+                batch = self._device_batch(kept, center, inner_square_edge_length, t)
+                ready = torch.cuda.Event(); ready.record(self._stream)
+        if offset_labels == "device":
+            for v in batch.values():
+                if torch.is_tensor(v):
+                    v.record_stream(main)
+            batch["_ready_event"] = ready
+            return batch
+        with torch.cuda.stream(self._stream):
             coords = b["coords"][:kept].clone(); inst = b["inst"][:kept].clone(); sem = b["sem"][:kept].clone()
             m_inner = b["m_inner"][:kept].bool(); m_sem = b["m_sem"][:kept].bool()
             if offset_labels == "host":
@@ -164,6 +177,22 @@ class PlotTiler:
                 v.record_stream(main)                      # allocated on the tiler's stream, consumed on the caller's
         batch["_ready_event"] = ready                      # consumers on another stream wait for this before reading the tile
         return batch
+
+
+    def _device_batch(self, kept, center, inner_square_edge_length, tile_index):
+        """`offset_labels="device"`: the batch of the cropped rows from one tl_train_item call in test mode (labels, masks and offset labels by
+        the device rule of include/treelearn_hip.h: rank 3 for the tree base, an exact sum), nothing copied to the host."""
+        from .device_dataset import ItemWorkspace, alloc_batch, train_item
+        b = self._buf; F = self.feats.shape[1]; dev = self.xyz.device
+        if getattr(self, "_item_ws", None) is None:
+            self._item_ws = ItemWorkspace(dev)
+        out = alloc_batch(kept, F, dev)
+        out["input_feats"].copy_(b["feats"][:kept, :F])
+        train_item(b["coords"][:kept], b["inst"][:kept].to(torch.int32), out, 0, float(inner_square_edge_length) / 2, self._item_ws,
+                   center=center.astype(np.float32))
+        out["batch_size"] = 1
+        out["tile_index"] = tile_index
+        return out
 
 
 # ------------------------------------------------------------------------------------------------ validation tiles on disk

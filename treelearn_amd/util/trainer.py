@@ -9,7 +9,7 @@
   ScalarLog      stands where the tensorboard SummaryWriter does: JSON lines in <work_dir>/scalars.jsonl
 
 The config keys are the reference's (configs/training/train.yaml over configs/_modular/{model,dataset_train,dataset_test}.yaml) plus an
-optional `seed`.  Crops come from util/crops.py, validation tiles from util/tiles.write_tiles; checkpoints are the reference's
+optional `seed` and an optional `device_batches` (default false: true builds the batches on the GPU, util/device_dataset.py).  Crops come from util/crops.py, validation tiles from util/tiles.write_tiles; checkpoints are the reference's
 {'net', 'optimizer', 'epoch'} files.  Not offered: distributed training (--dist).
 """
 import argparse
@@ -149,6 +149,8 @@ def train_epoch(config, epoch, model, optimizer, scheduler, scaler, train_loader
     for i, batch in enumerate(train_loader, start=1):
         if _get(config, "examples_per_epoch") < (i * batch_size):          # a fixed number of samples per epoch
             break
+        if batch.get("_ready_event") is not None:                          # device-resident batch produced on another stream (DeviceCropLoader)
+            torch.cuda.current_stream().wait_event(batch["_ready_event"])
         scheduler.step(epoch)
         optimizer.zero_grad()
         with torch.autocast("cuda", dtype=torch.float16, enabled=fp16):
@@ -210,11 +212,18 @@ def fit(config, resume=None, logger=None, writer=None):
     scheduler = build_cosine_scheduler(_get(config, "scheduler"), optimizer)
     scaler = _grad_scaler(bool(_get(config, "fp16")))
     ds_seed = {} if seed is None else dict(seed=int(seed))
-    train_set = CropDataset(**dict(ds_seed, **to_dict(_get(config, "dataset_train"))))
-    val_set = CropDataset(**dict(ds_seed, **to_dict(_get(config, "dataset_test"))))
     loaders = _get(config, "dataloader")
-    train_loader = build_dataloader(train_set, training=True, generator=generator, **to_dict(_get(loaders, "train")))
-    val_loader = build_dataloader(val_set, training=False, **to_dict(_get(loaders, "test")))
+    if _get(config, "device_batches", False):              # batches prepared on the GPU (util/device_dataset.py); num_workers does not apply
+        from .device_dataset import DeviceCropLoader
+        shuffle = generator if generator is not None else torch.Generator().manual_seed(int(torch.empty((), dtype=torch.int64).random_().item()))
+        train_loader = DeviceCropLoader(**dict(ds_seed, **to_dict(_get(config, "dataset_train"))), generator=shuffle,
+                                        batch_size=_get(_get(loaders, "train"), "batch_size", 1))
+        val_loader = DeviceCropLoader(**dict(ds_seed, **to_dict(_get(config, "dataset_test"))), batch_size=_get(_get(loaders, "test"), "batch_size", 1))
+    else:
+        train_set = CropDataset(**dict(ds_seed, **to_dict(_get(config, "dataset_train"))))
+        val_set = CropDataset(**dict(ds_seed, **to_dict(_get(config, "dataset_test"))))
+        train_loader = build_dataloader(train_set, training=True, generator=generator, **to_dict(_get(loaders, "train")))
+        val_loader = build_dataloader(val_set, training=False, **to_dict(_get(loaders, "test")))
 
     start_epoch = 1
     if resume:
