@@ -499,6 +499,34 @@ int tl_crops_extract(const float* xyz, const float* label, const float* feat, in
                      const double* rinv, double chunk_size, const int32_t* ws, int64_t capacity, float* out_xyz, int32_t* out_label,
                      float* out_feat, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ outlier removal on crops and tiles (csrc/tl_outlier.hip)
+ * sor_filter / rad_filter (tree_learn/util/data_preparation.py:589-614): open3d's remove_statistical_outlier and
+ * remove_radius_outlier, which SampleGenerator applies to every training crop (:281-287) and every tile (:446-454).  open3d is not
+ * part of the reference tree; the semantics below are the specification (restated from open3d 0.17 / nanoflann, parity unpinned).
+ * All arithmetic is f64 without fma contraction: d2(i, j) = (dx*dx + dy*dy) + dz*dz, d = sqrt(d2) correctly rounded.
+ *
+ * Grid: cell = floor((p - lo) / h) per axis, dims[a] cells (1 .. 2^21) along axis a; key = the three cell indices bit-interleaved
+ *   (Morton order, x highest).  The caller sorts the keys (keys_sorted) and gathers the points in that order (xyz_sorted f64[n,3]);
+ *   perm i64[n] = original row of sorted row.  Outputs are written in ORIGINAL row order.  Any h > 0 gives the same results.
+ * tl_outlier_keys: keys i64[n]; *err (device) = 1 when a point falls outside the grid (its key is then 0), else 0.
+ *   dims outside 1 .. 2^21 or h <= 0: TL_ERR_UNSUPPORTED (the caller grows the cell).
+ * tl_knn_mean_dist: avg[i] = (sum of the min(k, n) smallest d(i, .), point i itself included at 0, added in ascending order one
+ *   after the other) / min(k, n).  Bit-identical for any grid, launch geometry and row order.  k in 1..64, else TL_ERR_UNSUPPORTED.
+ * tl_sor_keep: mean = (sum of avg[i] over avg[i] > 0) / n; std = sqrt((sum of (avg[i] - mean)^2 over avg[i] > 0) / (n - 1));
+ *   *thr (device) = mean + std_ratio * std; keep[i] = avg[i] > 0 && avg[i] < thr.  n = 1 keeps nothing (*thr = 0).  Both sums are
+ *   fixed trees over fixed 2048-row chunks: no float atomics, the same bits run to run and for any grid size.
+ *   ws f64[tl_sor_ws_doubles(n)].
+ * tl_radius_count: count[i] = number of j, i included, with d2(i, j) < radius * radius (strict).  Needs h >= 1.0001 * radius
+ *   (else TL_ERR_ARG): the ball then lies inside the 27 cells around the point's own. */
+int tl_outlier_keys(const double* xyz, int64_t n, const double lo[3], double h, const int32_t dims[3], int64_t* keys, int32_t* err,
+                    tl_stream_t stream);
+int tl_knn_mean_dist(const double* xyz_sorted, const int64_t* keys_sorted, const int64_t* perm, int64_t n, const double lo[3], double h,
+                     const int32_t dims[3], int k, double* avg, tl_stream_t stream);
+int64_t tl_sor_ws_doubles(int64_t n);
+int tl_sor_keep(const double* avg, int64_t n, double std_ratio, uint8_t* keep, double* thr, double* ws, tl_stream_t stream);
+int tl_radius_count(const double* xyz_sorted, const int64_t* keys_sorted, const int64_t* perm, int64_t n, const double lo[3], double h,
+                    const int32_t dims[3], double radius, int32_t* count, tl_stream_t stream);
+
 /* ------------------------------------------------------------------ clustering
  * Replaces sklearn DBSCAN(eps, min_samples=2) in group_dbscan (tree_learn/util/pipeline.py:173-180):
  * connected components of the eps-graph on 2-D points; isolated points = -1; component labels

@@ -189,6 +189,11 @@ PROTOTYPES = {
     "tl_crops_ws_words": (_i64, [_i64, _i32]),
     "tl_crops_count": (_i32, [_vp, _i64, _i32, _vp, _vp, _c.c_double, _vp, _vp, _vp]),
     "tl_crops_extract": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _c.c_double, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "tl_outlier_keys": (_i32, [_vp, _i64, _c.c_double * 3, _c.c_double, _I3, _vp, _vp, _vp]),
+    "tl_knn_mean_dist": (_i32, [_vp, _vp, _vp, _i64, _c.c_double * 3, _c.c_double, _I3, _i32, _vp, _vp]),
+    "tl_sor_ws_doubles": (_i64, [_i64]),
+    "tl_sor_keep": (_i32, [_vp, _i64, _c.c_double, _vp, _vp, _vp, _vp]),
+    "tl_radius_count": (_i32, [_vp, _vp, _vp, _i64, _c.c_double * 3, _c.c_double, _I3, _c.c_double, _vp, _vp]),
     "tl_ring_classify": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 TL_EVAL_XY, TL_EVAL_Z = 0, 1

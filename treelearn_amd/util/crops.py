@@ -194,9 +194,14 @@ def check_occupancy(grid, centres, rinv, chunk_size, occupancy_res, min_percent_
     return sums.cpu().numpy(), ok.cpu().numpy().astype(bool)
 
 
-def extract_crops(points, labels, feats, centres, rinv, chunk_size, batch=MAX_BATCH):
+def extract_crops(points, labels, feats, centres, rinv, chunk_size, batch=MAX_BATCH, filters=None):
     """save's selection (data_preparation.py:264-289) for the chosen crops, in order: yields (points f32[n,3] = rotated xy and z,
-    instance_label int32[n], feat f32[n,F]) per crop, rows in plot order.  The plot is read once per `batch` crops."""
+    instance_label int32[n], feat f32[n,F]) per crop, rows in plot order.  The plot is read once per `batch` crops.
+    `filters` (a sample_generator section, or what outlier.active_filters returned): the outlier filters of :281-287, run on the
+    device on each extracted crop before it is copied to the host; they draw no random numbers and only remove rows."""
+    from . import outlier
+    filters = outlier.active_filters(filters)
+    denoise = filters["sor"] is not None or filters["rad"] is not None
     pts = _dev(points, torch.float32); lab = _dev(labels, torch.float32).reshape(-1)
     n = len(pts)
     ft = _dev(feats, torch.float32).reshape(n, -1)
@@ -218,8 +223,14 @@ def extract_crops(points, labels, feats, centres, rinv, chunk_size, batch=MAX_BA
         ofeat = torch.empty((cap, max(F, 1)), dtype=torch.float32, device=pts.device)
         _hip.check(L.tl_crops_extract(_hip.ptr(pts), _hip.ptr(lab), _hip.ptr(ft), n, F, nc, _hip.ptr(c), _hip.ptr(r), float(chunk_size), _hip.ptr(ws),
                                       cap, _hip.ptr(oxyz), _hip.ptr(olab), _hip.ptr(ofeat), _hip.stream()), "tl_crops_extract")
-        hx, hl, hf = oxyz.cpu().numpy(), olab.cpu().numpy(), ofeat[:, :F].cpu().numpy()
         off = np.concatenate([[0], np.cumsum(cnt)])
+        if denoise:
+            for i in range(nc):
+                a, e = int(off[i]), int(off[i + 1])
+                keep = outlier.denoise(oxyz[a:e], filters)
+                yield oxyz[a:e][keep].cpu().numpy(), olab[a:e][keep].cpu().numpy(), ofeat[a:e, :F][keep].cpu().numpy()
+            continue
+        hx, hl, hf = oxyz.cpu().numpy(), olab.cpu().numpy(), ofeat[:, :F].cpu().numpy()
         for i in range(nc):
             a, e = off[i], off[i + 1]
             yield hx[a:e], hl[a:e], hf[a:e]
@@ -253,10 +264,9 @@ def _load_plot(path_vox, path_feat):
 
 
 def check_cfg(cfg):
-    for k in _FILTER_KEYS:
-        if cfg.get(k) is not None:
-            raise NotImplementedError(f"{k} is set: open3d's outlier filters are not part of this project "
-                                      "(sample_generation.yaml leaves them off)")
+    """The outlier-filter pairs of the config (util/outlier.py): a complete pair is accepted, a half-set one refused by name."""
+    from .outlier import active_filters
+    return active_filters({k: cfg.get(k) for k in _FILTER_KEYS})
 
 
 def generate_random_crops(base_dir, cfg=None, seed=0, logger=None):
@@ -269,7 +279,7 @@ def generate_random_crops(base_dir, cfg=None, seed=0, logger=None):
     from .prepare import compute_features, voxelize
     from .segment import load_forest
     cfg = dict(TRAIN_CFG, **(cfg or {}))
-    check_cfg(cfg)
+    filters = check_cfg(cfg)
     rs = np.random.RandomState(seed)
     say = (lambda m: logger.info(m)) if logger is not None else (lambda m: None)
     forests_dir = osp.join(base_dir, "forests")
@@ -333,7 +343,7 @@ def generate_random_crops(base_dir, cfg=None, seed=0, logger=None):
             say(f"No valid candidates for plot {plot_name}")
             continue
         centres, angles, rinv = centres[ok][inds], angles[ok][inds], rinv[ok][inds]
-        crops = extract_crops(points, labels, feats, centres, rinv, cfg["chunk_size"])
+        crops = extract_crops(points, labels, feats, centres, rinv, cfg["chunk_size"], filters=filters)
         for k, (xyz, inst, feat) in enumerate(crops):
             center = centres[k]
             data = dict(points=xyz, feat=feat, instance_label=inst, center=np.array([center[0], center[1], 0]))
@@ -359,7 +369,13 @@ def parse_args(argv=None):
     for k in ("n_samples_total", "chunk_size", "occupancy_res", "n_points_to_calculate_occupancy", "how_far_fill", "min_percent_occupied_fill",
               "min_percent_occupied_choose", "voxel_size", "search_radius_features"):
         ap.add_argument("--" + k.replace("_", "-"), type=_number, default=TRAIN_CFG[k])
+    for k in _FILTER_KEYS:                                      # the outlier filters of util/outlier.py: off unless both keys of a pair are given
+        ap.add_argument("--" + k.replace("_", "-"), type=_number, default=None)
     a = ap.parse_args(argv)
+    try:
+        check_cfg({k: getattr(a, k) for k in _FILTER_KEYS})
+    except (NotImplementedError, ValueError) as e:
+        ap.error(str(e))
     for k in ("n_samples_total", "chunk_size", "occupancy_res", "n_points_to_calculate_occupancy", "voxel_size", "search_radius_features"):
         if not getattr(a, k) > 0:
             ap.error(f"--{k.replace('_', '-')} must be > 0")

@@ -179,7 +179,8 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
     feats = compute_features(vox, float(_get(sample_cfg, "search_radius_features", 0.6)))
     tiler = PlotTiler(vox, torch.full((len(vox),), -1.0, device=vox.device), feats)
     inner = float(_get(sample_cfg, "inner_edge"))
-    tiles = tiler.tiles(inner, float(_get(sample_cfg, "outer_edge")), float(_get(sample_cfg, "stride")), inner, offset_labels="none")
+    tiles = tiler.tiles(inner, float(_get(sample_cfg, "outer_edge")), float(_get(sample_cfg, "stride")), inner, offset_labels="none",
+                        sample_generator=_get(sample_cfg, "sample_generator"))
     _log(logger, "getting pointwise predictions")
     res = get_pointwise_preds(model, tiles, dict(voxel_size=vs), logger, keep_on_device=True)
     if len(res[4]) == 0 or not torch.is_tensor(res[4]):
@@ -301,6 +302,11 @@ def load_forest(path):
     return data
 
 
+def sample_generator_of(a):
+    """The `sample_generator` section of the parsed command line."""
+    return dict(n_neigh_sor=a.n_neigh_sor, multiplier_sor=a.multiplier_sor, rad=a.rad, npoints_rad=a.npoints_rad)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser("python -m treelearn_amd.util.segment", description="segment a forest point cloud into trees")
     ap.add_argument("--forest", required=True, help="input cloud: .npy / .npz / .txt, N x 3 or N x 4")
@@ -310,6 +316,10 @@ def parse_args(argv=None):
     ap.add_argument("--inner-edge", type=float, default=SAMPLE_CFG["inner_edge"])
     ap.add_argument("--outer-edge", type=float, default=SAMPLE_CFG["outer_edge"])
     ap.add_argument("--stride", type=float, default=SAMPLE_CFG["stride"])
+    ap.add_argument("--n-neigh-sor", type=int, default=None, help="statistical outlier filter on every tile: neighbours (with --multiplier-sor)")
+    ap.add_argument("--multiplier-sor", type=float, default=None, help="statistical outlier filter: standard-deviation ratio")
+    ap.add_argument("--rad", type=float, default=None, help="radius outlier filter on every tile: radius in metres (with --npoints-rad)")
+    ap.add_argument("--npoints-rad", type=int, default=None, help="radius outlier filter: a point is kept with more than this many points in the ball")
     ap.add_argument("--alpha", type=float, default=SHAPE_CFG["alpha"])
     ap.add_argument("--edge-buffer", type=float, default=SHAPE_CFG["buffer_size_to_determine_edge_trees"])
     ap.add_argument("--outer-remove", type=float, default=None, help="remove this many metres at the plot's xy outline (default: off)")
@@ -332,6 +342,11 @@ def parse_args(argv=None):
         ap.error("--outer-edge must be >= --inner-edge")
     if a.edge_buffer < 0 or (a.outer_remove is not None and a.outer_remove < 0):
         ap.error("buffer sizes must be >= 0")
+    try:
+        from .outlier import active_filters
+        active_filters(sample_generator_of(a))
+    except (NotImplementedError, ValueError) as e:
+        ap.error(str(e))
     if not os.path.exists(a.forest):
         ap.error(f"--forest {a.forest}: no such file")
     if not os.path.exists(a.weights):
@@ -351,7 +366,8 @@ def main(argv=None):
     model = TreeLearn(**dict(MODEL_CFG, voxel_size=a.voxel_size), compute_dtype=dt)
     load_checkpoint(a.weights, logger, model)
     model = model.cuda().eval()
-    sample = dict(SAMPLE_CFG, voxel_size=a.voxel_size, inner_edge=a.inner_edge, outer_edge=a.outer_edge, stride=a.stride)
+    sample = dict(SAMPLE_CFG, voxel_size=a.voxel_size, inner_edge=a.inner_edge, outer_edge=a.outer_edge, stride=a.stride,
+                  sample_generator=sample_generator_of(a))
     grouping = dict(GROUPING_CFG, use_hdbscan=a.grouping == "hdbscan", tau_min=a.tau_min, tau_group=a.tau_group,
                     tau_vert=a.tau_vert, tau_off=a.tau_off)
     shape = dict(SHAPE_CFG, alpha=a.alpha, buffer_size_to_determine_edge_trees=a.edge_buffer, outer_remove=a.outer_remove)

@@ -1,6 +1,6 @@
 """Device-resident inference tiling -- SURVEY.md 8f #3.
 
-Mirrors, for the pipeline's configuration (plot_corners=None, no tile denoising), the chain
+Mirrors, for the pipeline's configuration (plot_corners=None; tile denoising by util/outlier.py when its config keys are set), the chain
   SampleGenerator.tile_generate_and_save  (reference tree_learn/util/data_preparation.py:333-494)
   -> <plot>_<i>.npz -> TreeDataset.__getitem__ (test mode) -> collate_fn, batch size 1
      (tree_learn/dataset/dataset.py:34-76,167-226)
@@ -102,8 +102,11 @@ class PlotTiler:
                          inst=torch.empty(n, dtype=torch.int64, device=dev), sem=torch.empty(n, dtype=torch.int64, device=dev),
                          m_inner=torch.empty(n, dtype=torch.uint8, device=dev), m_sem=torch.empty(n, dtype=torch.uint8, device=dev))
 
-    def crop(self, inner, outer, inner_square_edge_length):
-        """One tile: (kept rows, rows in the inner square, centre f64[3]); the rows are in self._buf[...][:kept]."""
+    def crop(self, inner, outer, inner_square_edge_length, sample_generator=None):
+        """One tile: (kept rows, rows in the inner square, centre f64[3]); the rows are in self._buf[...][:kept].
+        `sample_generator` (the config section, or what outlier.active_filters returned): the outlier filters of
+        data_preparation.py:446-454 on the cropped, centred f32 coordinates; every per-row buffer is compacted with the one mask.
+        The inner-square count is the unfiltered one: the reference decides about an empty tile (:413-431) before it filters."""
         box = _hip.TileBox()
         i32 = inner.astype(np.float32)
         cx = np.round((i32[0] + i32[1]) / 2, 6); cy = np.round((i32[2] + i32[3]) / 2, 6)          # float32 arithmetic, data_preparation.py:431-434
@@ -117,21 +120,35 @@ class PlotTiler:
                                            _hip.ptr(b["m_inner"]), _hip.ptr(b["m_sem"]), _hip.ptr(self._count), _hip.ptr(self._ws), _hip.stream()),
                    "tl_tile_crop")
         kept, n_inner = (int(v) for v in self._count.cpu())
+        if sample_generator is not None and kept > 0:
+            from . import outlier
+            filters = outlier.active_filters(sample_generator)
+            if filters["sor"] is not None or filters["rad"] is not None:
+                rows = outlier.denoise(b["coords"][:kept], filters).nonzero().squeeze(1)
+                for buf in b.values():
+                    buf[:len(rows)] = buf[:kept].index_select(0, rows)
+                kept = len(rows)
         return kept, n_inner, np.array([float(cx), float(cy), 0.0])
 
-    def tiles(self, inner_edge, outer_edge, stride, inner_square_edge_length, offset_labels="host"):
-        """Generator of batch dicts (collate_fn's keys, batch size 1), in the reference's tile numbering."""
+    def tiles(self, inner_edge, outer_edge, stride, inner_square_edge_length, offset_labels="host", sample_generator=None):
+        """Generator of batch dicts (collate_fn's keys, batch size 1), in the reference's tile numbering.  `sample_generator`: the config
+        section whose complete pairs switch the outlier filters on (util/outlier.py); the numbering and the skipping of tiles do not change."""
         assert offset_labels in ("host", "none", "device")
+        if sample_generator is not None:
+            from .outlier import active_filters
+            sample_generator = active_filters(sample_generator)
         inner, outer = tile_grid(self.x_range, self.y_range, inner_edge, outer_edge, stride)
         F = self.feats.shape[1]
         main = torch.cuda.current_stream()
         self._stream.wait_stream(main)                         # the plot arrays may have just been produced on the caller's stream
         for t in range(len(inner)):                            # (one wait for the whole generator: a per-tile wait would put every crop behind the consumer's previous forward)
-            batch = self.tile_batch(inner[t], outer[t], inner_square_edge_length, offset_labels, tile_index=t, sync_with_caller=False)
+            batch = self.tile_batch(inner[t], outer[t], inner_square_edge_length, offset_labels, tile_index=t, sync_with_caller=False,
+                                    sample_generator=sample_generator)
             if batch is not None:
                 yield batch
 
-    def tile_batch(self, inner, outer, inner_square_edge_length, offset_labels="host", tile_index=0, sync_with_caller=True):
+    def tile_batch(self, inner, outer, inner_square_edge_length, offset_labels="host", tile_index=0, sync_with_caller=True,
+                   sample_generator=None):
         """ONE tile as a batch dict (collate_fn's keys, batch size 1) from its inner / outer square (x0, x1, y0, y1), or None when the inner
         square holds no point (data_preparation.py:412-427).  Random access for callers that own only some tiles of a plot (a rank of the
         sharded tile loop) or lay the squares out themselves.  `sync_with_caller=False`: the caller has already made the tiler's stream wait
@@ -145,7 +162,7 @@ class PlotTiler:
         # The crop (and its one host sync for the row count) goes on the tiler's own stream: a consumer that pulls the next
         # tile before launching the current forward (util/pipeline.get_pointwise_preds) then never waits for its own convs.
         with torch.cuda.stream(self._stream):
-            kept, n_inner, center = self.crop(np.asarray(inner, np.float64), np.asarray(outer, np.float64), inner_square_edge_length)
+            kept, n_inner, center = self.crop(np.asarray(inner, np.float64), np.asarray(outer, np.float64), inner_square_edge_length, sample_generator)
             if n_inner == 0:                               # data_preparation.py:412-427: tiles whose inner square is empty are dropped
                 return None
             b = self._buf
@@ -213,10 +230,8 @@ def write_tiles(forest_path, sample_cfg=None, logger=None):
     from .segment import load_forest
     cfg = dict(VAL_CFG, **{k: v for k, v in dict(sample_cfg or {}).items()})
     gen = dict(VAL_CFG["sample_generator"], **dict(cfg.get("sample_generator") or {}))
-    for k in _FILTER_KEYS:
-        if gen.get(k) is not None:
-            raise NotImplementedError(f"{k} is set: open3d's outlier filters are not part of this project "
-                                      "(sample_generation.yaml leaves them off)")
+    from .outlier import active_filters
+    filters = active_filters({k: gen.get(k) for k in _FILTER_KEYS})          # a half-set pair is refused here, before anything is written
     say = (lambda m: logger.info(m)) if logger is not None else (lambda m: None)
     plot_name = osp.basename(forest_path)[:-4]
     base_dir = osp.dirname(osp.dirname(osp.abspath(forest_path)))
@@ -253,7 +268,7 @@ def write_tiles(forest_path, sample_cfg=None, logger=None):
     i = 0
     for t in range(len(inner)):
         # the masks the crop also fills are not stored (the dataset derives them from the points), so their edge length does not matter here
-        kept, n_inner, center = tiler.crop(inner[t], outer[t], cfg["inner_edge"])
+        kept, n_inner, center = tiler.crop(inner[t], outer[t], cfg["inner_edge"], filters)
         if n_inner == 0:
             continue
         b = tiler._buf
@@ -274,6 +289,10 @@ def parse_args(argv=None):
     ap.add_argument("--inner-edge", type=float, default=VAL_CFG["inner_edge"])
     ap.add_argument("--outer-edge", type=float, default=VAL_CFG["outer_edge"])
     ap.add_argument("--stride", type=float, default=VAL_CFG["stride"])
+    ap.add_argument("--n-neigh-sor", type=int, default=None, help="statistical outlier filter on every tile: neighbours (with --multiplier-sor)")
+    ap.add_argument("--multiplier-sor", type=float, default=None, help="statistical outlier filter: standard-deviation ratio")
+    ap.add_argument("--rad", type=float, default=None, help="radius outlier filter on every tile: radius in metres (with --npoints-rad)")
+    ap.add_argument("--npoints-rad", type=int, default=None, help="radius outlier filter: a point is kept with more than this many points in the ball")
     a = ap.parse_args(argv)
     for k in ("voxel_size", "search_radius_features", "inner_edge", "outer_edge", "stride"):
         if not getattr(a, k) > 0:
@@ -289,8 +308,12 @@ def main(argv=None):
         return 2
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
     cfg = dict(voxel_size=a.voxel_size, search_radius_features=a.search_radius_features, inner_edge=a.inner_edge, outer_edge=a.outer_edge,
-               stride=a.stride)
-    n = write_tiles(a.forest, cfg, logger=logging.getLogger("treelearn_amd.tiles"))
+               stride=a.stride, sample_generator=dict(n_neigh_sor=a.n_neigh_sor, multiplier_sor=a.multiplier_sor, rad=a.rad, npoints_rad=a.npoints_rad))
+    try:
+        n = write_tiles(a.forest, cfg, logger=logging.getLogger("treelearn_amd.tiles"))
+    except NotImplementedError as e:                            # a half-set filter pair
+        print(str(e), file=sys.stderr)
+        return 2
     print(f"{n} tiles -> {osp.join(osp.dirname(osp.dirname(osp.abspath(a.forest))), 'tiles')}")
     return 0
 
