@@ -617,6 +617,39 @@ int tl_eval_partition(const double* xyz, const int64_t* gt, const int64_t* pred,
                       int64_t n_gt, const int64_t* pred_order, const int64_t* pred_start, int64_t n_pred, const int64_t* pairs, int64_t m,
                       const double* edges, int n_edges, int mode, int64_t* tp, int64_t* fp, int64_t* fn, double* norm, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ per-tree inventory of a labelled cloud (csrc/tl_inventory.hip)
+ * Position, height, stem diameter at breast height and crown cells of every tree of a segmented forest, on the device.  The semantics
+ * are the project's own (restated in numpy float64 in tests/inventory_restatement.py); all arithmetic is f64 in plain operators, no fma
+ * contraction.  The caller sorts the labels once (stable) and keeps the rows of labels >= 1: tree t (label t + 1) is rows
+ * start[t] .. start[t + 1] of the gathered cloud; an empty range is a tree without points.
+ * tl_inventory_gather: out_xyz f64[n,3], row j = columns 0..2 of row order[j] of pts (f32 or f64 by dtype_f64, row stride ld >= 3
+ *   elements, n_src rows), widened exactly; an index outside 0 .. n_src - 1 gives NaN.
+ * tl_tree_inventory: one workgroup per tree.  table f64[n_trees, 10] = z_low, z_top, height, x, y, z, dbh, dbh_x, dbh_y, dbh_rmse;
+ *   counts i64[n_trees, 2] = n_points, dbh_n.
+ *   z_low = the 4th smallest z, rank 3 with duplicates counted (the tree-base rule of tl_train_item), for more than 11 rows, else the
+ *   minimum; z_top = the 4th largest z for more than 11 rows, else the maximum; height = z_top - z_low.
+ *   (x, y, z) = mean of the base rows, z <= z_low + 0.5.
+ *   Slice rows: (z_low + slice_height) - slice_thickness / 2 <= z < (z_low + slice_height) + slice_thickness / 2 and w < dbh_max_radius^2,
+ *   u = x_row - x, v = y_row - y, w = u*u + v*v; dbh_n = their number.  Algebraic (Kasa) circle fit:
+ *   [[Suu, Suv, Su], [Suv, Svv, Sv], [Su, Sv, dbh_n]] [a, b, c]^T = [Suw, Svw, Sw] by Gaussian elimination with partial pivoting;
+ *   cx = a / 2, cy = b / 2, r2 = (c + cx*cx) + cy*cy; dbh = 2 sqrt(r2), dbh_x = cx + x, dbh_y = cy + y,
+ *   dbh_rmse = sqrt(sum((sqrt((u-cx)^2 + (v-cy)^2) - r)^2) / dbh_n).  These four are NaN when dbh_n < dbh_min_points, a pivot is below
+ *   1e-12 times the largest matrix entry, or r2 <= 0.  A tree without rows has n_points = 0 and NaN in all ten columns.
+ *   Sums: registers, a fixed wave butterfly, then the wave sums in wave order -- no float atomics, the same bits run to run.
+ * tl_crown_keys: keys i64[n] = (label << 42) | ((floor(x / cell) + 2^20) << 21) | (floor(y / cell) + 2^20) per gathered row (sorted_label
+ *   i64[n] = its label); *err (device) = 1 when a cell index is outside -2^20 .. 2^20 - 1 or a label outside 1 .. 2^21 - 1 (the key is
+ *   then 0 and the caller raises), else 0.
+ * tl_crown_count: cells i64[n_trees] (overwritten) = distinct keys of each tree among sorted_keys (ascending).  n_trees < 2^21.
+ * A null or misaligned pointer, a negative size, slice_thickness <= 0, dbh_max_radius <= 0 or cell <= 0: TL_ERR_ARG, nothing launched.
+ * n = 0 or n_trees = 0: TL_OK without a launch. */
+int tl_inventory_gather(const void* pts, int dtype_f64, int64_t ld, int64_t n_src, const int64_t* order, int64_t n, double* out_xyz,
+                        tl_stream_t stream);
+int tl_tree_inventory(const double* sorted_xyz, int64_t n, const int64_t* start, int64_t n_trees, double slice_height, double slice_thickness,
+                      double dbh_max_radius, int64_t dbh_min_points, double* table, int64_t* counts, tl_stream_t stream);
+int tl_crown_keys(const double* sorted_xyz, const int64_t* sorted_label, int64_t n, double cell, int64_t* keys, int32_t* err,
+                  tl_stream_t stream);
+int tl_crown_count(const int64_t* sorted_keys, int64_t n, int64_t n_trees, int64_t* cells, tl_stream_t stream);
+
 /* ------------------------------------------------------------------ validation metrics of a training run (csrc/tl_train_eval.hip)
  * Replaces `pointwise_eval` (tools/training/train.py:89-102) and the per-tile lists `validate` (:61-86) concatenates for it: called once
  * per validation tile, it ADDS that tile's share to a running state and keeps nothing per point.

@@ -175,6 +175,10 @@ PROTOTYPES = {
     "tl_knn_vote_grid": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _c.c_float * 3, _f32, _I3, _vp, _i64, _i32, _vp, _vp]),
     "tl_eval_contingency": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "tl_eval_partition": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "tl_inventory_gather": (_i32, [_vp, _i32, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "tl_tree_inventory": (_i32, [_vp, _i64, _vp, _i64, _c.c_double, _c.c_double, _c.c_double, _i64, _vp, _vp, _vp]),
+    "tl_crown_keys": (_i32, [_vp, _vp, _i64, _c.c_double, _vp, _vp, _vp]),
+    "tl_crown_count": (_i32, [_vp, _i64, _i64, _vp, _vp]),
     "tl_pointwise_eval_ws_bytes": (_i64, [_i64]),
     "tl_pointwise_eval": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "tl_point_jitter": (_i32, [_vp, _i64, _c.c_uint64, _vp]),

@@ -1,0 +1,250 @@
+"""Per-tree inventory of a segmented forest on the device: where each tree stands, how tall it is, its stem diameter at breast height
+(DBH) and how much ground its crown covers.
+
+    python -m treelearn_amd.util.inventory --forest labelled.npy|npz|txt --out trees.csv [--slice-height 1.3 ...]
+
+The semantics are the project's own; tests/inventory_restatement.py states them in numpy float64.  Trees are the labels 1..T with
+T = max(label); labels <= 0 are ignored; a label in 1..T without rows is a tree of n_points = 0 with NaN in every float column.
+
+  n_points
+  z_low, z_top    the 4th smallest / 4th largest z (rank 3, duplicates counted: the tree-base rule of tl_train_item) for more than 11 rows,
+                  else the minimum / maximum;  height = z_top - z_low
+  x, y, z         position: the float64 mean of the base rows, z <= z_low + 0.5 (the reference's position rule evaluated in float64; not
+                  bit-equal to the dataset's float32 np.mean)
+  dbh, dbh_x, dbh_y, dbh_n, dbh_rmse
+                  algebraic (Kasa) circle fit of the rows with z_low + slice_height - slice_thickness / 2 <= z < z_low + slice_height +
+                  slice_thickness / 2 within dbh_max_radius (horizontally) of the position: diameter, centre, rows used, rms radial residual.
+                  NaN (dbh_n still reported) for fewer than dbh_min_points rows, collinear or coincident rows, or a non-positive r^2.
+  crown_cells, crown_area, crown_diameter
+                  distinct (floor(x / c), floor(y / c)) cells of the tree's rows, c = crown_cell; area = cells * c^2; the diameter of the
+                  circle of that area.  The cells are those of the frame the coordinates are given in.
+
+One stable sort of the labels (torch) puts every tree's rows in one contiguous range; csrc/tl_inventory.hip gathers them as float64
+(tl_inventory_gather), runs one workgroup per tree (tl_tree_inventory) and counts the distinct crown keys (tl_crown_keys, a torch sort,
+tl_crown_count).  There is no CPU fallback."""
+import argparse
+import csv
+import sys
+import time
+
+import numpy as np
+
+DEFAULTS = dict(slice_height=1.3, slice_thickness=0.2, dbh_max_radius=1.0, dbh_min_points=8, crown_cell=0.25)
+COLUMNS = ("tree_id", "n_points", "x", "y", "z", "z_low", "z_top", "height", "dbh", "dbh_x", "dbh_y", "dbh_n", "dbh_rmse", "crown_cells",
+           "crown_area", "crown_diameter")
+INT_COLUMNS = ("tree_id", "n_points", "dbh_n", "crown_cells")
+_TABLE = ("z_low", "z_top", "height", "x", "y", "z", "dbh", "dbh_x", "dbh_y", "dbh_rmse")          # tl_tree_inventory's table columns
+_SHIFTED = (("x", 0), ("y", 1), ("z", 2), ("z_low", 2), ("z_top", 2), ("dbh_x", 0), ("dbh_y", 1))
+MAX_TREES = (1 << 21) - 1                                                                         # the tree field of a crown key
+
+__all__ = ["tree_inventory", "cloud_inventory", "write_inventory", "check_params", "DEFAULTS", "COLUMNS"]
+
+
+def check_params(cfg=None, **kw):
+    """The five parameters as a dict of plain numbers (defaults filled in); ValueError for an unknown name, a non-positive thickness,
+    radius or cell, a non-finite height or a negative point minimum.  Touches no GPU."""
+    p = dict(DEFAULTS)
+    for src in (cfg or {}), kw:
+        for k, v in src.items():
+            if k not in DEFAULTS:
+                raise ValueError(f"unknown inventory parameter {k!r}; expected one of {tuple(DEFAULTS)}")
+            if v is not None:
+                p[k] = v
+    for k in ("slice_thickness", "dbh_max_radius", "crown_cell"):
+        p[k] = float(p[k])
+        if not (p[k] > 0 and np.isfinite(p[k])):
+            raise ValueError(f"{k} must be > 0, got {p[k]!r}")
+    p["slice_height"] = float(p["slice_height"])
+    if not np.isfinite(p["slice_height"]):
+        raise ValueError(f"slice_height must be finite, got {p['slice_height']!r}")
+    if int(p["dbh_min_points"]) != p["dbh_min_points"] or int(p["dbh_min_points"]) < 0:
+        raise ValueError(f"dbh_min_points must be an integer >= 0, got {p['dbh_min_points']!r}")
+    p["dbh_min_points"] = int(p["dbh_min_points"])
+    return p
+
+
+def _offset(offset):
+    if offset is None:
+        return None
+    import torch
+    o = offset.detach().cpu().numpy() if torch.is_tensor(offset) else np.asarray(offset)
+    o = np.asarray(o, np.float64).reshape(-1)
+    if o.shape != (3,):
+        raise ValueError(f"offset must hold 3 values, got {o.shape}")
+    return o
+
+
+def _device_inputs(coords, labels):
+    """(coords on the device as given: f32 / f64 [N, >= 3] with unit column stride, labels i64 [N])."""
+    import torch
+    c = coords if torch.is_tensor(coords) else torch.from_numpy(np.asarray(coords))
+    if c.ndim != 2 or c.shape[1] not in (3, 4):
+        raise ValueError(f"coords must have shape [N, 3] (or [N, 4], the first three columns are used), got {tuple(c.shape)}")
+    if c.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"coords must be float32 or float64, got {c.dtype}")
+    lab = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(np.asarray(labels)).astype(np.int64, copy=False))
+    lab = lab.reshape(-1)
+    if lab.shape[0] != c.shape[0]:
+        raise ValueError(f"mismatched lengths: {c.shape[0]} coordinates for {lab.shape[0]} labels")
+    if not torch.cuda.is_available():
+        raise RuntimeError("treelearn_amd.util.inventory runs on the GPU (tl_tree_inventory); there is no CPU fallback")
+    c = c.to("cuda")
+    if len(c) and (c.stride(1) != 1 or c.stride(0) < 3):
+        c = c.contiguous()
+    return c, lab.to("cuda", torch.int64).contiguous()
+
+
+def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh_max_radius=1.0, dbh_min_points=8, crown_cell=0.25,
+                   offset=None, stages=None):
+    """coords [N, 3] float32 or float64 (a row stride of 3 or 4 elements is read in place), labels [N] integers; numpy arrays or tensors,
+    on the host or the device.  Returns a dict of numpy arrays of length T = max(label), keyed by COLUMNS (tree_id = 1..T).
+    `offset` (3 values) is added to x, y, z, z_low, z_top, dbh_x, dbh_y at the end -- the un-centring of segment_forest.
+    `stages`: a list that receives (name, seconds) per stage, each closed by a device synchronise (tools/dev_inventory.py)."""
+    p = check_params(slice_height=slice_height, slice_thickness=slice_thickness, dbh_max_radius=dbh_max_radius,
+                     dbh_min_points=dbh_min_points, crown_cell=crown_cell)
+    off = _offset(offset)
+    import torch
+    from .. import _hip
+    c, lab = _device_inputs(coords, labels)
+    L, dev, n = _hip.lib(), c.device, len(c)
+    t0 = [time.perf_counter()]
+
+    def mark(name):
+        if stages is not None:
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            stages.append((name, now - t0[0]))
+            t0[0] = now
+
+    # one stable sort; the rows of labels >= 1 in label order
+    vals, order = torch.sort(lab, stable=True)
+    T = max(int(vals[-1]), 0) if n else 0
+    if T > MAX_TREES:
+        raise ValueError(f"largest label {T}: the crown keys hold tree ids up to {MAX_TREES}")
+    edges = torch.searchsorted(vals, torch.arange(1, T + 2, dtype=torch.int64, device=dev))
+    first = int(edges[0]) if T else n
+    start = (edges - first).contiguous()
+    kept, kept_lab = order[first:].contiguous(), vals[first:].contiguous()
+    m = len(kept)
+    xyz = torch.empty((m, 3), dtype=torch.float64, device=dev)
+    if m:
+        _hip.check(L.tl_inventory_gather(_hip.ptr(c), int(c.dtype == torch.float64), c.stride(0), n, _hip.ptr(kept), m, _hip.ptr(xyz),
+                                         _hip.stream()), "tl_inventory_gather")
+    mark("sort + gather")
+
+    table = torch.empty((T, len(_TABLE)), dtype=torch.float64, device=dev)
+    counts = torch.empty((T, 2), dtype=torch.int64, device=dev)
+    if T:
+        _hip.check(L.tl_tree_inventory(_hip.ptr(xyz), m, _hip.ptr(start), T, p["slice_height"], p["slice_thickness"],
+                                       p["dbh_max_radius"], p["dbh_min_points"], _hip.ptr(table), _hip.ptr(counts), _hip.stream()),
+                   "tl_tree_inventory")
+    mark("kernel")
+
+    cells = torch.zeros(T, dtype=torch.int64, device=dev)
+    err = None
+    if m:
+        keys = torch.empty(m, dtype=torch.int64, device=dev)
+        err = torch.empty(1, dtype=torch.int32, device=dev)
+        _hip.check(L.tl_crown_keys(_hip.ptr(xyz), _hip.ptr(kept_lab), m, p["crown_cell"], _hip.ptr(keys), _hip.ptr(err), _hip.stream()),
+                   "tl_crown_keys")
+        keys = torch.sort(keys).values
+        _hip.check(L.tl_crown_count(_hip.ptr(keys), m, T, _hip.ptr(cells), _hip.stream()), "tl_crown_count")
+    mark("crown keys + count")
+
+    table_h, counts_h, cells_h = table.cpu().numpy(), counts.cpu().numpy(), cells.cpu().numpy()
+    bad = err is not None and int(err.item())
+    mark("D2H")
+    if bad:
+        raise ValueError(f"a coordinate is not finite or lies beyond 2^20 crown cells of {p['crown_cell']} m from the origin: centre the cloud")
+
+    out = {k: np.ascontiguousarray(table_h[:, j]) for j, k in enumerate(_TABLE)}
+    out["tree_id"] = np.arange(1, T + 1, dtype=np.int64)
+    out["n_points"], out["dbh_n"], out["crown_cells"] = np.ascontiguousarray(counts_h[:, 0]), np.ascontiguousarray(counts_h[:, 1]), cells_h
+    cell = np.float64(p["crown_cell"])
+    area = cells_h.astype(np.float64) * (cell * cell)
+    area[out["n_points"] == 0] = np.nan
+    out["crown_area"] = area
+    out["crown_diameter"] = 2 * np.sqrt(area / np.pi)
+    if off is not None:
+        for k, a in _SHIFTED:
+            out[k] = out[k] + off[a]
+    return {k: out[k] for k in COLUMNS}
+
+
+def cloud_inventory(points, **params):
+    """The inventory of an N x 4 cloud (x y z label), as the command line computes it: the coordinates are centred on their float64 mean
+    on the device, as segment_forest centres its input, and the mean is handed back as `offset`."""
+    import torch
+    pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points))
+    if pts.ndim != 2 or pts.shape[1] != 4:
+        raise ValueError(f"expected an N x 4 cloud (x y z label), got {tuple(pts.shape)}")
+    check_params(**params)
+    if not torch.cuda.is_available():
+        raise RuntimeError("treelearn_amd.util.inventory runs on the GPU (tl_tree_inventory); there is no CPU fallback")
+    pts = pts.to("cuda")
+    xyz = pts[:, :3].to(torch.float64)
+    if len(xyz) == 0:
+        return tree_inventory(xyz, pts[:, 3].to(torch.int64), **params)
+    mean = xyz.mean(0)
+    return tree_inventory(xyz - mean, pts[:, 3].to(torch.int64), offset=mean, **params)
+
+
+def write_inventory(path, inv, categories=None):
+    """CSV: a header row, then one row per tree; floats as repr (they read back to the same bits), NaN as `nan`.  `categories` (per tree:
+    index into segment.CATEGORIES) adds a `category` column of names."""
+    T = len(inv["tree_id"])
+    names = None
+    if categories is not None:
+        from .segment import CATEGORIES
+        cat = np.asarray(categories).reshape(-1)
+        if len(cat) != T:
+            raise ValueError(f"{len(cat)} categories for {T} trees")
+        names = [CATEGORIES[int(v)] for v in cat]
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(list(COLUMNS) + (["category"] if names is not None else []))
+        for i in range(T):
+            row = [str(int(inv[k][i])) if k in INT_COLUMNS else repr(float(inv[k][i])) for k in COLUMNS]
+            w.writerow(row + ([names[i]] if names is not None else []))
+    return path
+
+
+def add_arguments(ap):
+    """The five parameters as command-line options (shared with util.segment)."""
+    ap.add_argument("--slice-height", type=float, default=DEFAULTS["slice_height"], help="height of the DBH slice above the tree base, metres")
+    ap.add_argument("--slice-thickness", type=float, default=DEFAULTS["slice_thickness"], help="thickness of the DBH slice, metres")
+    ap.add_argument("--dbh-max-radius", type=float, default=DEFAULTS["dbh_max_radius"], help="slice rows farther than this from the tree position are left out")
+    ap.add_argument("--dbh-min-points", type=int, default=DEFAULTS["dbh_min_points"], help="fewer slice rows than this: no DBH")
+    ap.add_argument("--crown-cell", type=float, default=DEFAULTS["crown_cell"], help="edge of the crown-cover cells, metres")
+
+
+def params_of(a):
+    return {k: getattr(a, k) for k in DEFAULTS}
+
+
+def main(argv=None):
+    import os
+    ap = argparse.ArgumentParser("python -m treelearn_amd.util.inventory", description="per-tree inventory (position, height, DBH, crown) of a labelled cloud")
+    ap.add_argument("--forest", required=True, help="labelled cloud: .npy / .npz / .txt, N x 4 (x y z label)")
+    ap.add_argument("--out", required=True, help="CSV to write")
+    add_arguments(ap)
+    a = ap.parse_args(argv)
+    try:
+        params = check_params(params_of(a))
+    except ValueError as e:
+        ap.error(str(e))
+    if not os.path.exists(a.forest):
+        ap.error(f"--forest {a.forest}: no such file")
+    from .segment import load_forest
+    data = load_forest(a.forest)
+    if data.shape[1] != 4:
+        ap.error(f"--forest {a.forest}: expected N x 4 (x y z label), got {data.shape}")
+    inv = cloud_inventory(data, **params)
+    write_inventory(a.out, inv)
+    ok = int(np.isfinite(inv["dbh"]).sum())
+    print(f"{a.forest}: {len(data)} points, {len(inv['tree_id'])} trees, {ok} with a DBH -> {a.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

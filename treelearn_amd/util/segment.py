@@ -158,9 +158,14 @@ def segment_from_pointwise(coords, offset_predictions, instance_preds, shape_cfg
 
 
 def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=None, return_type="original", logger=None,
-                   return_pointwise=False):
+                   return_pointwise=False, inventory=False, inventory_cfg=None):
     """points: N x 3 or N x 4 (x y z [label]) f64, host or device.  Returns numpy arrays: coords (f64, input frame), labels (i64),
-    categories (per tree 1..T, index into CATEGORIES), and with return_pointwise the arrays of pipeline.py:100-111 (ensembled rows)."""
+    categories (per tree 1..T, index into CATEGORIES), and with return_pointwise the arrays of pipeline.py:100-111 (ensembled rows).
+    inventory=True adds result["inventory"]: util.inventory.tree_inventory of the returned coords / labels, computed on the device in
+    the centred frame and un-centred like the coords; inventory_cfg holds any of its five parameters."""
+    if inventory:
+        from .inventory import check_params, tree_inventory
+        inventory_cfg = check_params(inventory_cfg)                                   # before any GPU work
     sample_cfg = dict(SAMPLE_CFG, **(sample_cfg or {})) if isinstance(sample_cfg, (dict, type(None))) else sample_cfg
     grouping_cfg = dict(GROUPING_CFG, **(grouping_cfg or {})) if isinstance(grouping_cfg, (dict, type(None))) else grouping_cfg
     shape_cfg = dict(SHAPE_CFG, **(shape_cfg or {})) if isinstance(shape_cfg, (dict, type(None))) else shape_cfg
@@ -200,6 +205,9 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
     r = segment_from_pointwise(coords, off, inst, shape_cfg, return_type, trace=trace, voxels=vox, points=centred, logger=logger)
     host = lambda t: t.cpu().numpy()                                                  # noqa: E731
     result = dict(coords=host(r["coords"] + mean), labels=host(r["labels"]), categories=host(r["categories"]))
+    if inventory:
+        _log(logger, "computing the tree inventory")
+        result["inventory"] = tree_inventory(r["coords"], r["labels"], offset=mean, **inventory_cfg)
     if return_pointwise:
         pw = dict(coords=coords, offset_predictions=off, offset_labels=offl, semantic_prediction_logits=sem, semantic_labels=seml,
                   instance_labels=instl, backbone_feats=bb, input_feats=infeat, instance_preds=inst, instance_preds_after_initial_clustering=initial)
@@ -252,7 +260,8 @@ def save_data(data, save_format, save_name, save_folder, use_offset=True):
 def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewise=True, save_pointwise=False):
     """The reference's results layout under out_dir: full_forest/<plot_name>.<fmt> for every format; individual_trees/<category>/<id>.<fmt>
     and individual_trees/non_trees.<fmt> (first format; coordinates shifted by the mean of the returned cloud, as save_treewise does);
-    pointwise_results/pointwise_results.npz + cluster_coords_initial / cluster_coords (first format) when the result holds them."""
+    pointwise_results/pointwise_results.npz + cluster_coords_initial / cluster_coords (first format) when the result holds them;
+    tree_inventory.csv (util.inventory.write_inventory, with the category names) when the result holds an inventory."""
     save_formats = list(save_formats)
     check_formats(save_formats)
     coords, labels = np.asarray(result["coords"], np.float64), np.asarray(result["labels"], np.int64)
@@ -280,6 +289,10 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
                 save_data(d, save_formats[0], "non_trees", trees_dir, use_offset=False)
             elif 1 <= i <= len(cats):
                 save_data(d, save_formats[0], str(int(i)), os.path.join(trees_dir, CATEGORIES[int(cats[i - 1])]), use_offset=False)
+    if "inventory" in result:
+        from .inventory import write_inventory
+        os.makedirs(out_dir, exist_ok=True)
+        write_inventory(os.path.join(out_dir, "tree_inventory.csv"), result["inventory"], categories=result["categories"])
     if save_pointwise and "pointwise" in result:
         pw = result["pointwise"]
         pdir = os.path.join(out_dir, "pointwise_results")
@@ -333,7 +346,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-treewise", action="store_true", help="do not write individual_trees/")
     ap.add_argument("--save-pointwise", action="store_true", help="write pointwise_results/")
     ap.add_argument("--dtype", choices=("fp32", "bf16", "fp16"), default="fp32", help="network compute dtype")
+    ap.add_argument("--inventory", action="store_true", help="write tree_inventory.csv: position, height, DBH and crown cover of every tree")
+    from .inventory import add_arguments, check_params, params_of
+    add_arguments(ap)
     a = ap.parse_args(argv)
+    try:
+        check_params(params_of(a))
+    except ValueError as e:
+        ap.error(str(e))
     check_formats(a.formats)
     for k in ("voxel_size", "inner_edge", "outer_edge", "stride"):
         if not getattr(a, k) > 0:
@@ -372,7 +392,9 @@ def main(argv=None):
                     tau_vert=a.tau_vert, tau_off=a.tau_off)
     shape = dict(SHAPE_CFG, alpha=a.alpha, buffer_size_to_determine_edge_trees=a.edge_buffer, outer_remove=a.outer_remove)
     with torch.no_grad():
-        res = segment_forest(points, model, sample, grouping, shape, a.return_type, logger, return_pointwise=a.save_pointwise)
+        from .inventory import params_of
+        res = segment_forest(points, model, sample, grouping, shape, a.return_type, logger, return_pointwise=a.save_pointwise,
+                             inventory=a.inventory, inventory_cfg=params_of(a) if a.inventory else None)
     plot_name = os.path.splitext(os.path.basename(a.forest))[0]
     save_results(res, a.out, plot_name, a.formats, save_treewise=not a.no_treewise, save_pointwise=a.save_pointwise)
     cats = np.bincount(res["categories"], minlength=3)
