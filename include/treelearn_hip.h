@@ -650,6 +650,46 @@ int tl_crown_keys(const double* sorted_xyz, const int64_t* sorted_label, int64_t
                   tl_stream_t stream);
 int tl_crown_count(const int64_t* sorted_keys, int64_t n, int64_t n_trees, int64_t* cells, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ terrain model of a labelled cloud (csrc/tl_terrain.hip)
+ * A raster of ground heights (DTM) from the non-tree rows of a segmented forest, the ground under any point, and the per-tree columns
+ * measured from that ground.  The semantics are the project's own (restated in numpy float64 in tests/terrain_restatement.py); all
+ * arithmetic is f64 in plain operators, no fma contraction.  The grid is row-major [ny, nx], nx, ny <= 32768, nx * ny <= 2^26; a row's
+ * cell is (floor(x / cell) - ix0, floor(y / cell) - iy0); the centre of cell i is ((ix0 + i) + 0.5) * cell.
+ * tl_dtm_min: pts f32 or f64 by dtype_f64, row stride ld >= 3 elements, n rows, widened exactly; labels i64[n] or NULL.  Candidates are
+ *   the rows with label 0 (every row when labels is NULL).  keys u64[ny, nx] (overwritten) = the order-preserving image of the lowest
+ *   candidate z of the cell (sign bit set for z >= 0, all bits flipped for z < 0), all-ones for a cell without a candidate;
+ *   n_candidates i32[ny, nx] (overwritten) = candidates per cell.  Integer atomics only: exact, the same bits for any row order.
+ *   *err (device) = 1 when a coordinate is not finite or a row lies outside the grid (that row is skipped and the caller raises), else 0.
+ * tl_dtm_filter: zmin f64[ny, nx] = the decoded minimum (NaN for a cell without one); state u8[ny, nx] = 0 empty, 2 rejected, 1 ground.
+ *   A cell p with a minimum is rejected when another cell q with a minimum, within Chebyshev distance `window`, has
+ *   zmin[p] - zmin[q] > max_slope * (cell * sqrt(di*di + dj*dj)) + step_tol (strict; evaluated against the raw minima, one pass).
+ * tl_dtm_fill: z f64[ny, nx], state u8[ny, nx] from zmin / state_in (distinct buffers).  A ground cell keeps its minimum and state 1.
+ *   Any other cell takes, at the first Chebyshev radius rho = 1 .. fill_radius whose window holds a ground cell, sum(w z) / sum(w) over
+ *   the ground cells of that window in row-major order, w = 1 / (di*di + dj*dj), and state 3 (was empty) or 4 (was rejected); without
+ *   such a radius NaN and its state (0 or 2).
+ * tl_dtm_sample: per row, u = x / cell - (ix0 + 0.5), i0 = floor(u), fx = u - i0, i0 and i0 + 1 clamped to 0 .. nx - 1, the same in y;
+ *   with four finite corners (g00 (1 - fx) + g10 fx) (1 - fy) + (g01 (1 - fx) + g11 fx) fy, else the value of the cell that contains
+ *   the point (indices clamped), NaN included; NaN for a non-finite x or y or an empty grid.  ground f64[n] and / or hag f64[n] = z - ground
+ *   (either may be NULL, not both; ld >= 2, >= 3 with hag).
+ * tl_tree_ground (csrc/tl_inventory.hip): one workgroup per tree over the ranges of tl_tree_inventory, whose `table` it reads (z_low,
+ *   z_top, x, y), with z_ground f64[n_trees] = the ground sampled at (x, y).  ground_table f64[n_trees, 7] = z_ground, height_ag =
+ *   z_top - z_ground, base_gap = z_low - z_ground, dbh_ag, dbh_ag_x, dbh_ag_y, dbh_ag_rmse; ground_n i64[n_trees] = dbh_ag_n: the slice,
+ *   fit and NaN rules of tl_tree_inventory with z_ground in place of z_low (the same device functions).  A NaN z_ground or a tree
+ *   without rows: NaN in all seven, ground_n = 0.
+ * A null or misaligned pointer, a negative size, a grid beyond the limits, cell <= 0, max_slope < 0, step_tol < 0, window < 0,
+ * fill_radius < 0, slice_thickness <= 0 or dbh_max_radius <= 0: TL_ERR_ARG, nothing launched.  n = 0, n_trees = 0 or an empty grid:
+ * TL_OK without a kernel launch. */
+int tl_dtm_min(const void* pts, int dtype_f64, int64_t ld, int64_t n, const int64_t* labels, double cell, int64_t ix0, int64_t iy0, int nx, int ny,
+               uint64_t* keys, int32_t* n_candidates, int32_t* err, tl_stream_t stream);
+int tl_dtm_filter(const uint64_t* keys, int nx, int ny, double cell, double max_slope, double step_tol, int window, double* zmin, uint8_t* state,
+                  tl_stream_t stream);
+int tl_dtm_fill(const double* zmin, const uint8_t* state_in, int nx, int ny, int fill_radius, double* z, uint8_t* state, tl_stream_t stream);
+int tl_dtm_sample(const void* pts, int dtype_f64, int64_t ld, int64_t n, const double* z, double cell, int64_t ix0, int64_t iy0, int nx, int ny,
+                  double* ground, double* hag, tl_stream_t stream);
+int tl_tree_ground(const double* sorted_xyz, int64_t n, const int64_t* start, int64_t n_trees, const double* table, const double* z_ground,
+                   double slice_height, double slice_thickness, double dbh_max_radius, int64_t dbh_min_points, double* ground_table,
+                   int64_t* ground_n, tl_stream_t stream);
+
 /* ------------------------------------------------------------------ validation metrics of a training run (csrc/tl_train_eval.hip)
  * Replaces `pointwise_eval` (tools/training/train.py:89-102) and the per-tile lists `validate` (:61-86) concatenates for it: called once
  * per validation tile, it ADDS that tile's share to a running state and keeps nothing per point.

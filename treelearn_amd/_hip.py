@@ -179,6 +179,11 @@ PROTOTYPES = {
     "tl_tree_inventory": (_i32, [_vp, _i64, _vp, _i64, _c.c_double, _c.c_double, _c.c_double, _i64, _vp, _vp, _vp]),
     "tl_crown_keys": (_i32, [_vp, _vp, _i64, _c.c_double, _vp, _vp, _vp]),
     "tl_crown_count": (_i32, [_vp, _i64, _i64, _vp, _vp]),
+    "tl_dtm_min": (_i32, [_vp, _i32, _i64, _i64, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "tl_dtm_filter": (_i32, [_vp, _i32, _i32, _c.c_double, _c.c_double, _c.c_double, _i32, _vp, _vp, _vp]),
+    "tl_dtm_fill": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "tl_dtm_sample": (_i32, [_vp, _i32, _i64, _i64, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "tl_tree_ground": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _c.c_double, _c.c_double, _c.c_double, _i64, _vp, _vp, _vp]),
     "tl_pointwise_eval_ws_bytes": (_i64, [_i64]),
     "tl_pointwise_eval": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "tl_point_jitter": (_i32, [_vp, _i64, _c.c_uint64, _vp]),

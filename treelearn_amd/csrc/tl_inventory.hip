@@ -3,6 +3,7 @@
 // tl_inventory_gather: the rows of the tree labels, widened to f64 and written in label order, so that a tree is one contiguous range.
 // tl_tree_inventory:   one workgroup per tree, four trips over its range: (a) the four lowest / highest z -> z_low, z_top; (b) the base
 //   sums -> position; (c) the slice moments -> one lane solves the 3 x 3 system of the algebraic circle fit; (d) the residual sum.
+// tl_tree_ground:      one workgroup per tree, trips (c) and (d) again with the terrain's ground under the tree in place of z_low.
 // tl_crown_keys / tl_crown_count: one packed (tree, cell x, cell y) key per row; distinct keys per tree counted on the sorted keys.
 // Every formula is f64 in plain operators under the pragma below (no contraction into fma), so every predicate sees the value numpy
 // sees.  Sums go registers -> wave shuffles -> LDS in a fixed order and counts are integers: two runs give the same bits.
@@ -14,6 +15,7 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 constexpr int kCols = 10;                    // z_low, z_top, height, x, y, z, dbh, dbh_x, dbh_y, dbh_rmse
+constexpr int kGroundCols = 7;               // z_ground, height_ag, base_gap, dbh_ag, dbh_ag_x, dbh_ag_y, dbh_ag_rmse
 constexpr int kCellBits = 21;                // cell index + 2^20 in 0 .. 2^21 - 1; tree id in the 21 bits above both
 constexpr int64_t kCellHalf = (int64_t)1 << (kCellBits - 1);
 
@@ -107,6 +109,51 @@ __device__ Fit kasa_solve(const double (&m)[9], double cnt) {
   return f;
 }
 
+// Trips (c) and (d) over the rows lo .. hi of one tree, by the whole workgroup: the moments of the slice rows (zc - half_thickness <= z <
+// zc + half_thickness, within r2max of (px, py) horizontally), one lane solves the 3 x 3 system and broadcasts the circle through
+// s_fit (3 doubles) and s_ok, then the residual sum.  Every thread returns the same fit, cnt (slice rows) and rss.  s_red: kWaves * 9.
+__device__ __forceinline__ Fit slice_circle(const double* __restrict__ xyz, int64_t lo, int64_t hi, double px, double py, double zc,
+                                            double half_thickness, double r2max, int64_t min_points, double* __restrict__ s_red,
+                                            double* __restrict__ s_fit, int* __restrict__ s_ok, double& cnt, double& rss) {
+  const int tid = threadIdx.x;
+  const double z0 = zc - half_thickness, z1 = zc + half_thickness;
+  double m[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // Suu Suv Svv Su Sv Suw Svw Sw count
+  for (int64_t j = lo + tid; j < hi; j += kBlock) {
+    const double z = xyz[3 * j + 2];
+    if (!(z >= z0 && z < z1)) continue;
+    const double u = xyz[3 * j] - px, v = xyz[3 * j + 1] - py;
+    const double w = u * u + v * v;
+    if (!(w < r2max)) continue;
+    m[0] = m[0] + u * u; m[1] = m[1] + u * v; m[2] = m[2] + v * v; m[3] = m[3] + u; m[4] = m[4] + v;
+    m[5] = m[5] + u * w; m[6] = m[6] + v * w; m[7] = m[7] + w; m[8] = m[8] + 1.0;
+  }
+  block_sum<9>(m, s_red);
+  cnt = m[8];                                                  // an exact integer: fewer than 2^53 rows
+  if (tid == 0) {                                              // one lane solves the 3 x 3 system
+    Fit g{0.0, 0.0, 0.0, 0};
+    if (cnt >= (double)min_points && cnt > 0.0) g = kasa_solve(m, cnt);
+    s_fit[0] = g.cx; s_fit[1] = g.cy; s_fit[2] = g.r; *s_ok = g.ok;
+  }
+  __syncthreads();
+  const Fit f{s_fit[0], s_fit[1], s_fit[2], *s_ok};
+  // residuals of the fitted circle over the slice rows
+  double e[1] = {0.0};
+  if (f.ok) {
+    for (int64_t j = lo + tid; j < hi; j += kBlock) {
+      const double z = xyz[3 * j + 2];
+      if (!(z >= z0 && z < z1)) continue;
+      const double u = xyz[3 * j] - px, v = xyz[3 * j + 1] - py;
+      if (!(u * u + v * v < r2max)) continue;
+      const double du = u - f.cx, dv = v - f.cy;
+      const double d = sqrt(du * du + dv * dv) - f.r;
+      e[0] = e[0] + d * d;
+    }
+  }
+  block_sum<1>(e, s_red);
+  rss = e[0];
+  return f;
+}
+
 __global__ void __launch_bounds__(kBlock) k_tree_inventory(const double* __restrict__ xyz, int64_t n, const int64_t* __restrict__ start,
                                                            double slice_height, double half_thickness, double r2max, int64_t min_points,
                                                            double* __restrict__ table, int64_t* __restrict__ counts) {
@@ -166,52 +213,53 @@ __global__ void __launch_bounds__(kBlock) k_tree_inventory(const double* __restr
     px = v[0] / v[3]; py = v[1] / v[3]; pz = v[2] / v[3];
   }
 
-  // (c) slice moments
-  const double zc = z_low + slice_height;
-  const double z0 = zc - half_thickness, z1 = zc + half_thickness;
-  double m[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // Suu Suv Svv Su Sv Suw Svw Sw count
-  for (int64_t j = lo + tid; j < hi; j += kBlock) {
-    const double z = xyz[3 * j + 2];
-    if (!(z >= z0 && z < z1)) continue;
-    const double u = xyz[3 * j] - px, v = xyz[3 * j + 1] - py;
-    const double w = u * u + v * v;
-    if (!(w < r2max)) continue;
-    m[0] = m[0] + u * u; m[1] = m[1] + u * v; m[2] = m[2] + v * v; m[3] = m[3] + u; m[4] = m[4] + v;
-    m[5] = m[5] + u * w; m[6] = m[6] + v * w; m[7] = m[7] + w; m[8] = m[8] + 1.0;
-  }
-  block_sum<9>(m, s_red);
-  const double cnt = m[8];                                     // an exact integer: fewer than 2^53 rows
-  if (tid == 0) {                                              // one lane solves the 3 x 3 system
-    Fit g{0.0, 0.0, 0.0, 0};
-    if (cnt >= (double)min_points && cnt > 0.0) g = kasa_solve(m, cnt);
-    s_par[2] = g.cx; s_par[3] = g.cy; s_par[4] = g.r; s_ok = g.ok;
-  }
-  __syncthreads();
-  const Fit f{s_par[2], s_par[3], s_par[4], s_ok};
-
-  // (d) residuals of the fitted circle over the slice rows
-  double e[1] = {0.0};
-  if (f.ok) {
-    for (int64_t j = lo + tid; j < hi; j += kBlock) {
-      const double z = xyz[3 * j + 2];
-      if (!(z >= z0 && z < z1)) continue;
-      const double u = xyz[3 * j] - px, v = xyz[3 * j + 1] - py;
-      if (!(u * u + v * v < r2max)) continue;
-      const double du = u - f.cx, dv = v - f.cy;
-      const double d = sqrt(du * du + dv * dv) - f.r;
-      e[0] = e[0] + d * d;
-    }
-  }
-  block_sum<1>(e, s_red);
+  // (c) slice moments and fit, (d) residuals
+  double cnt, rss;
+  const Fit f = slice_circle(xyz, lo, hi, px, py, z_low + slice_height, half_thickness, r2max, min_points, s_red, s_par + 2, &s_ok, cnt, rss);
   if (tid == 0) {
     out[0] = z_low; out[1] = z_top; out[2] = z_top - z_low;
     out[3] = px; out[4] = py; out[5] = pz;
     out[6] = f.ok ? 2.0 * f.r : nan;
     out[7] = f.ok ? f.cx + px : nan;
     out[8] = f.ok ? f.cy + py : nan;
-    out[9] = f.ok ? sqrt(e[0] / cnt) : nan;
+    out[9] = f.ok ? sqrt(rss / cnt) : nan;
     counts[2 * t] = rows;
     counts[2 * t + 1] = (int64_t)cnt;
+  }
+}
+
+// The slice fit of every tree once more, with the ground under the tree (z_ground, sampled from the terrain at the tree's position)
+// in place of z_low.  table: tl_tree_inventory's.  out f64[n_trees, 7] = z_ground, height_ag, base_gap, dbh_ag, dbh_ag_x, dbh_ag_y,
+// dbh_ag_rmse; out_n i64[n_trees] = dbh_ag_n.
+__global__ void __launch_bounds__(kBlock) k_tree_ground(const double* __restrict__ xyz, int64_t n, const int64_t* __restrict__ start,
+                                                        const double* __restrict__ table, const double* __restrict__ z_ground, double slice_height,
+                                                        double half_thickness, double r2max, int64_t min_points, double* __restrict__ out,
+                                                        int64_t* __restrict__ out_n) {
+  __shared__ double s_red[kWaves * 9];
+  __shared__ double s_fit[3];
+  __shared__ int s_ok;
+  const int tid = threadIdx.x;
+  const int64_t t = blockIdx.x;
+  int64_t lo = start[t], hi = start[t + 1];
+  if (lo < 0 || hi > n || lo > hi) { lo = 0; hi = 0; }        // a malformed range reads nothing
+  const double nan = __builtin_nan("");
+  const double zg = z_ground[t];
+  double* o = out + t * kGroundCols;
+  if (hi == lo || !(zg == zg)) {                               // block-uniform: no rows, or no terrain under the tree
+    if (tid < kGroundCols) o[tid] = nan;
+    if (tid == 0) out_n[t] = 0;
+    return;
+  }
+  const double z_low = table[t * kCols], z_top = table[t * kCols + 1], px = table[t * kCols + 3], py = table[t * kCols + 4];
+  double cnt, rss;
+  const Fit f = slice_circle(xyz, lo, hi, px, py, zg + slice_height, half_thickness, r2max, min_points, s_red, s_fit, &s_ok, cnt, rss);
+  if (tid == 0) {
+    o[0] = zg; o[1] = z_top - zg; o[2] = z_low - zg;
+    o[3] = f.ok ? 2.0 * f.r : nan;
+    o[4] = f.ok ? f.cx + px : nan;
+    o[5] = f.ok ? f.cy + py : nan;
+    o[6] = f.ok ? sqrt(rss / cnt) : nan;
+    out_n[t] = (int64_t)cnt;
   }
 }
 
@@ -264,6 +312,21 @@ extern "C" int tl_tree_inventory(const double* sorted_xyz, int64_t n, const int6
   if (n_trees == 0) return TL_OK;
   k_tree_inventory<<<(unsigned)n_trees, kBlock, 0, tl_s(stream)>>>(sorted_xyz, n, start, slice_height, slice_thickness / 2.0,
                                                                     dbh_max_radius * dbh_max_radius, dbh_min_points, table, counts);
+  TL_CHECK_LAUNCH();
+  return TL_OK;
+}
+
+extern "C" int tl_tree_ground(const double* sorted_xyz, int64_t n, const int64_t* start, int64_t n_trees, const double* table,
+                              const double* z_ground, double slice_height, double slice_thickness, double dbh_max_radius, int64_t dbh_min_points,
+                              double* ground_table, int64_t* ground_n, tl_stream_t stream) {
+  if (!sorted_xyz || !start || !table || !z_ground || !ground_table || !ground_n || n < 0 || n_trees < 0 || n_trees >= ((int64_t)1 << 31))
+    return TL_ERR_ARG;
+  if (!aligned8(sorted_xyz) || !aligned8(start) || !aligned8(table) || !aligned8(z_ground) || !aligned8(ground_table) || !aligned8(ground_n))
+    return TL_ERR_ARG;
+  if (!(slice_thickness > 0.0) || !(dbh_max_radius > 0.0) || !(slice_height == slice_height) || dbh_min_points < 0) return TL_ERR_ARG;
+  if (n_trees == 0) return TL_OK;
+  k_tree_ground<<<(unsigned)n_trees, kBlock, 0, tl_s(stream)>>>(sorted_xyz, n, start, table, z_ground, slice_height, slice_thickness / 2.0,
+                                                                 dbh_max_radius * dbh_max_radius, dbh_min_points, ground_table, ground_n);
   TL_CHECK_LAUNCH();
   return TL_OK;
 }

@@ -21,7 +21,11 @@ T = max(label); labels <= 0 are ignored; a label in 1..T without rows is a tree 
 
 One stable sort of the labels (torch) puts every tree's rows in one contiguous range; csrc/tl_inventory.hip gathers them as float64
 (tl_inventory_gather), runs one workgroup per tree (tl_tree_inventory) and counts the distinct crown keys (tl_crown_keys, a torch sort,
-tl_crown_count).  There is no CPU fallback."""
+tl_crown_count).  There is no CPU fallback.
+
+With a terrain (util.terrain) the eight GROUND_COLUMNS follow the sixteen: z_ground (the terrain sampled at the tree's x, y),
+height_ag = z_top - z_ground, base_gap = z_low - z_ground, and dbh_ag, dbh_ag_x, dbh_ag_y, dbh_ag_n, dbh_ag_rmse: the slice fit above with
+z_ground in place of z_low (tl_tree_ground).  NaN, and dbh_ag_n = 0, where the terrain has no value under the tree."""
 import argparse
 import csv
 import sys
@@ -35,9 +39,12 @@ COLUMNS = ("tree_id", "n_points", "x", "y", "z", "z_low", "z_top", "height", "db
 INT_COLUMNS = ("tree_id", "n_points", "dbh_n", "crown_cells")
 _TABLE = ("z_low", "z_top", "height", "x", "y", "z", "dbh", "dbh_x", "dbh_y", "dbh_rmse")          # tl_tree_inventory's table columns
 _SHIFTED = (("x", 0), ("y", 1), ("z", 2), ("z_low", 2), ("z_top", 2), ("dbh_x", 0), ("dbh_y", 1))
+GROUND_COLUMNS = ("z_ground", "height_ag", "base_gap", "dbh_ag", "dbh_ag_x", "dbh_ag_y", "dbh_ag_n", "dbh_ag_rmse")
+_GROUND_TABLE = ("z_ground", "height_ag", "base_gap", "dbh_ag", "dbh_ag_x", "dbh_ag_y", "dbh_ag_rmse")       # tl_tree_ground's table columns
+_GROUND_SHIFTED = (("z_ground", 2), ("dbh_ag_x", 0), ("dbh_ag_y", 1))
 MAX_TREES = (1 << 21) - 1                                                                         # the tree field of a crown key
 
-__all__ = ["tree_inventory", "cloud_inventory", "write_inventory", "check_params", "DEFAULTS", "COLUMNS"]
+__all__ = ["tree_inventory", "cloud_inventory", "write_inventory", "check_params", "DEFAULTS", "COLUMNS", "GROUND_COLUMNS"]
 
 
 def check_params(cfg=None, **kw):
@@ -95,11 +102,13 @@ def _device_inputs(coords, labels):
 
 
 def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh_max_radius=1.0, dbh_min_points=8, crown_cell=0.25,
-                   offset=None, stages=None):
+                   offset=None, stages=None, terrain=None):
     """coords [N, 3] float32 or float64 (a row stride of 3 or 4 elements is read in place), labels [N] integers; numpy arrays or tensors,
     on the host or the device.  Returns a dict of numpy arrays of length T = max(label), keyed by COLUMNS (tree_id = 1..T).
     `offset` (3 values) is added to x, y, z, z_low, z_top, dbh_x, dbh_y at the end -- the un-centring of segment_forest.
-    `stages`: a list that receives (name, seconds) per stage, each closed by a device synchronise (tools/dev_inventory.py)."""
+    `stages`: a list that receives (name, seconds) per stage, each closed by a device synchronise (tools/dev_inventory.py).
+    `terrain`: a util.terrain.Terrain in the frame of `coords`; the dict then holds GROUND_COLUMNS after COLUMNS (`offset` is added to
+    z_ground, dbh_ag_x, dbh_ag_y as well)."""
     p = check_params(slice_height=slice_height, slice_thickness=slice_thickness, dbh_max_radius=dbh_max_radius,
                      dbh_min_points=dbh_min_points, crown_cell=crown_cell)
     off = _offset(offset)
@@ -140,6 +149,16 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
                    "tl_tree_inventory")
     mark("kernel")
 
+    if terrain is not None:
+        gtable = torch.empty((T, len(_GROUND_TABLE)), dtype=torch.float64, device=dev)
+        gcount = torch.empty(T, dtype=torch.int64, device=dev)
+        if T:
+            zg = terrain.sample(table[:, 3:5])                                        # the positions, read in place from the table
+            _hip.check(L.tl_tree_ground(_hip.ptr(xyz), m, _hip.ptr(start), T, _hip.ptr(table), _hip.ptr(zg), p["slice_height"],
+                                        p["slice_thickness"], p["dbh_max_radius"], p["dbh_min_points"], _hip.ptr(gtable), _hip.ptr(gcount),
+                                        _hip.stream()), "tl_tree_ground")
+        mark("ground columns")
+
     cells = torch.zeros(T, dtype=torch.int64, device=dev)
     err = None
     if m:
@@ -152,6 +171,8 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     mark("crown keys + count")
 
     table_h, counts_h, cells_h = table.cpu().numpy(), counts.cpu().numpy(), cells.cpu().numpy()
+    if terrain is not None:
+        gtable_h, gcount_h = gtable.cpu().numpy(), gcount.cpu().numpy()
     bad = err is not None and int(err.item())
     mark("D2H")
     if bad:
@@ -168,31 +189,46 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     if off is not None:
         for k, a in _SHIFTED:
             out[k] = out[k] + off[a]
-    return {k: out[k] for k in COLUMNS}
+    if terrain is None:
+        return {k: out[k] for k in COLUMNS}
+    out.update({k: np.ascontiguousarray(gtable_h[:, j]) for j, k in enumerate(_GROUND_TABLE)})
+    out["dbh_ag_n"] = gcount_h
+    if off is not None:
+        for k, a in _GROUND_SHIFTED:
+            out[k] = out[k] + off[a]
+    return {k: out[k] for k in COLUMNS + GROUND_COLUMNS}
 
 
-def cloud_inventory(points, **params):
+def cloud_inventory(points, terrain=False, terrain_cfg=None, **params):
     """The inventory of an N x 4 cloud (x y z label), as the command line computes it: the coordinates are centred on their float64 mean
-    on the device, as segment_forest centres its input, and the mean is handed back as `offset`."""
+    on the device, as segment_forest centres its input, and the mean is handed back as `offset`.  terrain=True builds the terrain of
+    the label-0 rows in the same frame (util.terrain.terrain_model, parameters in terrain_cfg) and adds the GROUND_COLUMNS."""
     import torch
     pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points))
     if pts.ndim != 2 or pts.shape[1] != 4:
         raise ValueError(f"expected an N x 4 cloud (x y z label), got {tuple(pts.shape)}")
     check_params(**params)
+    if terrain:
+        from .terrain import check_params as check_terrain, terrain_model
+        terrain_cfg = check_terrain(terrain_cfg)
     if not torch.cuda.is_available():
         raise RuntimeError("treelearn_amd.util.inventory runs on the GPU (tl_tree_inventory); there is no CPU fallback")
     pts = pts.to("cuda")
-    xyz = pts[:, :3].to(torch.float64)
+    xyz, lab = pts[:, :3].to(torch.float64), pts[:, 3].to(torch.int64)
     if len(xyz) == 0:
-        return tree_inventory(xyz, pts[:, 3].to(torch.int64), **params)
+        return tree_inventory(xyz, lab, terrain=terrain_model(xyz, lab, **terrain_cfg) if terrain else None, **params)
     mean = xyz.mean(0)
-    return tree_inventory(xyz - mean, pts[:, 3].to(torch.int64), offset=mean, **params)
+    centred = xyz - mean
+    return tree_inventory(centred, lab, offset=mean, terrain=terrain_model(centred, lab, **terrain_cfg) if terrain else None, **params)
 
 
 def write_inventory(path, inv, categories=None):
     """CSV: a header row, then one row per tree; floats as repr (they read back to the same bits), NaN as `nan`.  `categories` (per tree:
-    index into segment.CATEGORIES) adds a `category` column of names."""
+    index into segment.CATEGORIES) adds a `category` column of names.  The columns are those the dict holds: COLUMNS, and GROUND_COLUMNS
+    after them when the inventory was taken with a terrain."""
     T = len(inv["tree_id"])
+    columns = COLUMNS + (GROUND_COLUMNS if all(k in inv for k in GROUND_COLUMNS) else ())
+    ints = INT_COLUMNS + ("dbh_ag_n",)
     names = None
     if categories is not None:
         from .segment import CATEGORIES
@@ -202,9 +238,9 @@ def write_inventory(path, inv, categories=None):
         names = [CATEGORIES[int(v)] for v in cat]
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(list(COLUMNS) + (["category"] if names is not None else []))
+        w.writerow(list(columns) + (["category"] if names is not None else []))
         for i in range(T):
-            row = [str(int(inv[k][i])) if k in INT_COLUMNS else repr(float(inv[k][i])) for k in COLUMNS]
+            row = [str(int(inv[k][i])) if k in ints else repr(float(inv[k][i])) for k in columns]
             w.writerow(row + ([names[i]] if names is not None else []))
     return path
 
@@ -228,9 +264,13 @@ def main(argv=None):
     ap.add_argument("--forest", required=True, help="labelled cloud: .npy / .npz / .txt, N x 4 (x y z label)")
     ap.add_argument("--out", required=True, help="CSV to write")
     add_arguments(ap)
+    ap.add_argument("--terrain", action="store_true", help="add the ground columns: terrain from the label-0 rows, height and DBH from the ground")
+    from . import terrain as _terrain
+    _terrain.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         params = check_params(params_of(a))
+        terrain_cfg = _terrain.check_params(_terrain.params_of(a))
     except ValueError as e:
         ap.error(str(e))
     if not os.path.exists(a.forest):
@@ -239,7 +279,7 @@ def main(argv=None):
     data = load_forest(a.forest)
     if data.shape[1] != 4:
         ap.error(f"--forest {a.forest}: expected N x 4 (x y z label), got {data.shape}")
-    inv = cloud_inventory(data, **params)
+    inv = cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, **params)
     write_inventory(a.out, inv)
     ok = int(np.isfinite(inv["dbh"]).sum())
     print(f"{a.forest}: {len(data)} points, {len(inv['tree_id'])} trees, {ok} with a DBH -> {a.out}")

@@ -158,14 +158,20 @@ def segment_from_pointwise(coords, offset_predictions, instance_preds, shape_cfg
 
 
 def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=None, return_type="original", logger=None,
-                   return_pointwise=False, inventory=False, inventory_cfg=None):
+                   return_pointwise=False, inventory=False, inventory_cfg=None, terrain=False, terrain_cfg=None):
     """points: N x 3 or N x 4 (x y z [label]) f64, host or device.  Returns numpy arrays: coords (f64, input frame), labels (i64),
     categories (per tree 1..T, index into CATEGORIES), and with return_pointwise the arrays of pipeline.py:100-111 (ensembled rows).
     inventory=True adds result["inventory"]: util.inventory.tree_inventory of the returned coords / labels, computed on the device in
-    the centred frame and un-centred like the coords; inventory_cfg holds any of its five parameters."""
+    the centred frame and un-centred like the coords; inventory_cfg holds any of its five parameters.
+    terrain=True adds result["terrain"] (util.terrain: the DTM of the label-0 rows of the returned cloud, computed on the device in the
+    centred frame; the un-centred Terrain.to_host()) and result["height_above_ground"] (f64 [N], row-aligned with coords); terrain_cfg
+    holds any of its five parameters.  With inventory=True as well, the inventory gets the ground columns."""
     if inventory:
         from .inventory import check_params, tree_inventory
         inventory_cfg = check_params(inventory_cfg)                                   # before any GPU work
+    if terrain:
+        from .terrain import check_params as check_terrain, terrain_model
+        terrain_cfg = check_terrain(terrain_cfg)
     sample_cfg = dict(SAMPLE_CFG, **(sample_cfg or {})) if isinstance(sample_cfg, (dict, type(None))) else sample_cfg
     grouping_cfg = dict(GROUPING_CFG, **(grouping_cfg or {})) if isinstance(grouping_cfg, (dict, type(None))) else grouping_cfg
     shape_cfg = dict(SHAPE_CFG, **(shape_cfg or {})) if isinstance(shape_cfg, (dict, type(None))) else shape_cfg
@@ -205,9 +211,15 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
     r = segment_from_pointwise(coords, off, inst, shape_cfg, return_type, trace=trace, voxels=vox, points=centred, logger=logger)
     host = lambda t: t.cpu().numpy()                                                  # noqa: E731
     result = dict(coords=host(r["coords"] + mean), labels=host(r["labels"]), categories=host(r["categories"]))
+    dtm = None
+    if terrain:
+        _log(logger, "computing the terrain model")
+        dtm = terrain_model(r["coords"], r["labels"], offset=mean, **terrain_cfg)
+        result["terrain"] = dtm.to_host()
+        result["height_above_ground"] = host(dtm.height_above_ground(r["coords"]))
     if inventory:
         _log(logger, "computing the tree inventory")
-        result["inventory"] = tree_inventory(r["coords"], r["labels"], offset=mean, **inventory_cfg)
+        result["inventory"] = tree_inventory(r["coords"], r["labels"], offset=mean, terrain=dtm, **inventory_cfg)
     if return_pointwise:
         pw = dict(coords=coords, offset_predictions=off, offset_labels=offl, semantic_prediction_logits=sem, semantic_labels=seml,
                   instance_labels=instl, backbone_feats=bb, input_feats=infeat, instance_preds=inst, instance_preds_after_initial_clustering=initial)
@@ -261,7 +273,8 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
     """The reference's results layout under out_dir: full_forest/<plot_name>.<fmt> for every format; individual_trees/<category>/<id>.<fmt>
     and individual_trees/non_trees.<fmt> (first format; coordinates shifted by the mean of the returned cloud, as save_treewise does);
     pointwise_results/pointwise_results.npz + cluster_coords_initial / cluster_coords (first format) when the result holds them;
-    tree_inventory.csv (util.inventory.write_inventory, with the category names) when the result holds an inventory."""
+    tree_inventory.csv (util.inventory.write_inventory, with the category names) when the result holds an inventory; terrain.npz
+    (util.terrain.write_terrain) and height_above_ground.npy when it holds a terrain."""
     save_formats = list(save_formats)
     check_formats(save_formats)
     coords, labels = np.asarray(result["coords"], np.float64), np.asarray(result["labels"], np.int64)
@@ -293,6 +306,11 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
         from .inventory import write_inventory
         os.makedirs(out_dir, exist_ok=True)
         write_inventory(os.path.join(out_dir, "tree_inventory.csv"), result["inventory"], categories=result["categories"])
+    if "terrain" in result:
+        from .terrain import write_terrain
+        os.makedirs(out_dir, exist_ok=True)
+        write_terrain(os.path.join(out_dir, "terrain.npz"), result["terrain"])
+        np.save(os.path.join(out_dir, "height_above_ground.npy"), np.asarray(result["height_above_ground"], np.float64))
     if save_pointwise and "pointwise" in result:
         pw = result["pointwise"]
         pdir = os.path.join(out_dir, "pointwise_results")
@@ -349,9 +367,13 @@ def parse_args(argv=None):
     ap.add_argument("--inventory", action="store_true", help="write tree_inventory.csv: position, height, DBH and crown cover of every tree")
     from .inventory import add_arguments, check_params, params_of
     add_arguments(ap)
+    ap.add_argument("--terrain", action="store_true", help="write terrain.npz and height_above_ground.npy; with --inventory, add the ground columns")
+    from . import terrain as _terrain
+    _terrain.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         check_params(params_of(a))
+        _terrain.check_params(_terrain.params_of(a))
     except ValueError as e:
         ap.error(str(e))
     check_formats(a.formats)
@@ -392,9 +414,11 @@ def main(argv=None):
                     tau_vert=a.tau_vert, tau_off=a.tau_off)
     shape = dict(SHAPE_CFG, alpha=a.alpha, buffer_size_to_determine_edge_trees=a.edge_buffer, outer_remove=a.outer_remove)
     with torch.no_grad():
+        from . import terrain as _terrain
         from .inventory import params_of
         res = segment_forest(points, model, sample, grouping, shape, a.return_type, logger, return_pointwise=a.save_pointwise,
-                             inventory=a.inventory, inventory_cfg=params_of(a) if a.inventory else None)
+                             inventory=a.inventory, inventory_cfg=params_of(a) if a.inventory else None,
+                             terrain=a.terrain, terrain_cfg=_terrain.params_of(a) if a.terrain else None)
     plot_name = os.path.splitext(os.path.basename(a.forest))[0]
     save_results(res, a.out, plot_name, a.formats, save_treewise=not a.no_treewise, save_pointwise=a.save_pointwise)
     cats = np.bincount(res["categories"], minlength=3)
