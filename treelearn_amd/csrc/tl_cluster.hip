@@ -10,7 +10,7 @@
 // itself with every earlier point within eps (lock-free union-find, larger root hooked under the
 // smaller => root = smallest index of the component).  Distances are evaluated in fp64 on the fp32
 // inputs, as sklearn's KD-tree does.  HBM/latency-bound integer work; no MFMA.
-#include "tl_common.h"
+#include "tl_scan.h"
 
 namespace {
 
@@ -81,22 +81,6 @@ __global__ void __launch_bounds__(kBlock) k_insert(const float* __restrict__ xy,
   }
 }
 
-__device__ __forceinline__ int find_root(int* parent, int x) {
-  while (true) {
-    const int p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (p == x) return x;
-    x = p;
-  }
-}
-__device__ __forceinline__ void unite(int* parent, int a, int b) {
-  while (true) {
-    a = find_root(parent, a); b = find_root(parent, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }          // hook the larger root under the smaller
-    if (atomicCAS(&parent[a], a, b) == a) return;
-  }
-}
-
 __global__ void __launch_bounds__(kBlock) k_link(const float* __restrict__ xy, int64_t n, double inv_eps, double eps2, Ws w) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float xf = xy[2 * i], yf = xy[2 * i + 1];
@@ -118,7 +102,7 @@ __global__ void __launch_bounds__(kBlock) k_link(const float* __restrict__ xy, i
           const double ddx = (double)xy[2 * (int64_t)j] - x, ddy = (double)xy[2 * (int64_t)j + 1] - y;
           if (ddx * ddx + ddy * ddy <= eps2) {
             any = true;
-            if (j < (int)i) unite(w.parent, (int)i, j);      // each edge once
+            if (j < (int)i) tl_unite(w.parent, (int)i, j);      // each edge once
           }
         }
       }
@@ -128,51 +112,10 @@ __global__ void __launch_bounds__(kBlock) k_link(const float* __restrict__ xy, i
 
 __global__ void __launch_bounds__(kBlock) k_flatten(int64_t n, Ws w) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int r = find_root(w.parent, (int)i);
+    const int r = tl_find_root(w.parent, (int)i);
     w.flag[i] = (r == (int)i && w.linked[i]) ? 1 : 0;
     w.linked[i] = w.linked[i] ? r : -1;                        // reuse: root of the point, or -1 for noise
   }
-}
-
-// exclusive scan of flag[] (3 passes, 2048 items per block)
-constexpr int kItems = 8, kTile = kBlock * kItems;
-__device__ __forceinline__ int block_scan(int v, int* total) {
-  __shared__ int wsum[kBlock / 64];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int inc = v;
-  for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(inc, off); if (lane >= off) inc += t; }
-  if (lane == 63) wsum[wid] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-  for (int q = 0; q < kBlock / 64; ++q) { if (q < wid) base += wsum[q]; tot += wsum[q]; }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
-__global__ void __launch_bounds__(kBlock) k_scan1(const int* __restrict__ f, int64_t n, int* __restrict__ part) {
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
-  int s = 0;
-  for (int j = 0; j < kItems; ++j) if (base + j < n) s += f[base + j];
-  int tot; block_scan(s, &tot);
-  if (threadIdx.x == 0) part[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(kBlock) k_scan2(int* __restrict__ part, int64_t nb, int* __restrict__ total) {
-  int carry = 0;
-  for (int64_t b0 = 0; b0 < nb; b0 += kBlock) {
-    const int64_t i = b0 + threadIdx.x;
-    const int v = i < nb ? part[i] : 0;
-    int tot; const int ex = block_scan(v, &tot);
-    if (i < nb) part[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
-__global__ void __launch_bounds__(kBlock) k_scan3(int* __restrict__ f, int64_t n, const int* __restrict__ part) {
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
-  int c[kItems]; int s = 0;
-  for (int j = 0; j < kItems; ++j) { c[j] = (base + j < n) ? f[base + j] : 0; s += c[j]; }
-  int tot; int ex = block_scan(s, &tot) + part[blockIdx.x];
-  for (int j = 0; j < kItems; ++j) { if (base + j < n) f[base + j] = ex; ex += c[j]; }
 }
 
 __global__ void __launch_bounds__(kBlock) k_labels(int64_t n, Ws w, int32_t* __restrict__ labels) {
@@ -189,7 +132,7 @@ extern "C" {
 int64_t tl_cluster_ws_bytes(int64_t n) {
   if (n <= 0) return 0;
   const int64_t H = table_size(n);
-  return align16(H * 8) + align16(H * 4) + 4 * align16(n * 4) + align16((tl_cdiv(n, kTile) + 1) * 4) + 64;
+  return align16(H * 8) + align16(H * 4) + 4 * align16(n * 4) + align16(tl_scan_parts_words(n) * 4) + 64;
 }
 
 int tl_cluster_grid(const float* xy, int64_t n, double eps, int32_t* labels, int32_t* n_clusters, void* ws, tl_stream_t stream) {
@@ -201,10 +144,7 @@ int tl_cluster_grid(const float* xy, int64_t n, double eps, int32_t* labels, int
   k_insert<<<tl_grid(n, kBlock), kBlock, 0, s>>>(xy, n, inv, w);
   k_link<<<(unsigned)tl_cdiv(n, kBlock), kBlock, 0, s>>>(xy, n, inv, eps * eps, w);
   k_flatten<<<tl_grid(n, kBlock), kBlock, 0, s>>>(n, w);
-  const int64_t nb = tl_cdiv(n, kTile);
-  k_scan1<<<(unsigned)nb, kBlock, 0, s>>>(w.flag, n, w.part);
-  k_scan2<<<1, kBlock, 0, s>>>(w.part, nb, n_clusters);
-  k_scan3<<<(unsigned)nb, kBlock, 0, s>>>(w.flag, n, w.part);
+  tl_launch_scan_i32(w.flag, n, w.flag, n_clusters, w.part, s);     // root flags -> cluster ids, in place
   k_labels<<<tl_grid(n, kBlock), kBlock, 0, s>>>(n, w, labels);
   TL_CHECK_LAUNCH();
   return TL_OK;

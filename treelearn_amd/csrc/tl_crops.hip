@@ -9,27 +9,13 @@
 // Exactness: f64 wherever the reference is f64, plain operators in the reference's order under the
 // pragma below (no fma contraction), no division in the step search.  The reference's ±3 m view boxes
 // (generate_views, :548-561) only preselect a superset of the rotated square and are not restated.
-#include "tl_common.h"
+#include "tl_scan.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kItems = 8, kTile = 256 * kItems, kMaxCrops = 32;
-
-__device__ __forceinline__ uint32_t block_scan2(uint32_t v, uint32_t* total) {
-  __shared__ uint32_t wsum[4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  uint32_t inc = v;
-  for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)inc, off); if (lane >= off) inc += t; }
-  if (lane == 63) wsum[wid] = inc;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-  for (int w = 0; w < 4; ++w) { if (w < wid) base += wsum[w]; tot += wsum[w]; }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
+constexpr int kMaxCrops = 32;
 
 // first k in [0, m) with steps[k] >= v (m when none): steps ascending, f64 compare of the widened f32 value
 __device__ __forceinline__ int lower_bound(const double* __restrict__ steps, int m, double v) {
@@ -85,7 +71,7 @@ __global__ void __launch_bounds__(256) k_check(const double* __restrict__ cx, in
     double u, v;
     if (occ[c] && in_square(cx[i] - ox, cy[j] - oy, r, half, &u, &v)) ++cnt;
   }
-  uint32_t tot; block_scan2(cnt, &tot);
+  uint32_t tot; tl_block_scan<4>(cnt, &tot);
   if (threadIdx.x == 0) {
     const double s = (double)tot;
     if (sum) sum[k] = s;
@@ -120,33 +106,17 @@ __global__ void __launch_bounds__(256) k_crop_partials(const float* __restrict__
                                                        const double* __restrict__ rinv, double half, int32_t* __restrict__ part, int64_t nb) {
   __shared__ CropSet cs;
   load_set(cs, centre, rinv, nc);
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
-  uint32_t bits[kItems];
-  for (int j = 0; j < kItems; ++j) {
+  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+  uint32_t bits[kScanItems];
+  for (int j = 0; j < kScanItems; ++j) {
     bits[j] = 0;
     if (base + j < n) bits[j] = crop_bits(cs, nc, xyz[(base + j) * 3], xyz[(base + j) * 3 + 1], half);
   }
   for (int c = 0; c < nc; ++c) {
     uint32_t s = 0;
-    for (int j = 0; j < kItems; ++j) s += (bits[j] >> c) & 1u;
-    uint32_t tot; block_scan2(s, &tot);
+    for (int j = 0; j < kScanItems; ++j) s += (bits[j] >> c) & 1u;
+    uint32_t tot; tl_block_scan<4>(s, &tot);
     if (threadIdx.x == 0) part[c * nb + blockIdx.x] = (int32_t)tot;
-  }
-}
-
-// one block: exclusive scan over part in crop-major order (crop c's rows follow crop c-1's), per-crop counts
-__global__ void __launch_bounds__(256) k_crop_scan(int32_t* __restrict__ part, int64_t nb, int nc, int32_t* __restrict__ count) {
-  uint32_t carry = 0;
-  for (int c = 0; c < nc; ++c) {
-    const uint32_t start = carry;
-    for (int64_t b0 = 0; b0 < nb; b0 += 256) {
-      const int64_t i = b0 + threadIdx.x;
-      const uint32_t v = i < nb ? (uint32_t)part[c * nb + i] : 0u;
-      uint32_t tot; const uint32_t ex = block_scan2(v, &tot);
-      if (i < nb) part[c * nb + i] = (int32_t)(carry + ex);
-      carry += tot;
-    }
-    if (threadIdx.x == 0) count[c] = (int32_t)(carry - start);
   }
 }
 
@@ -157,17 +127,17 @@ __global__ void __launch_bounds__(256) k_crop_scatter(const float* __restrict__ 
                                                       float* __restrict__ out_xyz, int32_t* __restrict__ out_label, float* __restrict__ out_feat) {
   __shared__ CropSet cs;
   load_set(cs, centre, rinv, nc);
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
-  uint32_t bits[kItems];
-  for (int j = 0; j < kItems; ++j) {
+  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+  uint32_t bits[kScanItems];
+  for (int j = 0; j < kScanItems; ++j) {
     bits[j] = 0;
     if (base + j < n) bits[j] = crop_bits(cs, nc, xyz[(base + j) * 3], xyz[(base + j) * 3 + 1], half);
   }
   for (int c = 0; c < nc; ++c) {
     uint32_t s = 0;
-    for (int j = 0; j < kItems; ++j) s += (bits[j] >> c) & 1u;
-    uint32_t tot; int64_t pos = (int64_t)block_scan2(s, &tot) + (uint32_t)part[c * nb + blockIdx.x];
-    for (int j = 0; j < kItems; ++j)
+    for (int j = 0; j < kScanItems; ++j) s += (bits[j] >> c) & 1u;
+    uint32_t tot; int64_t pos = (int64_t)tl_block_scan<4>(s, &tot) + (uint32_t)part[c * nb + blockIdx.x];
+    for (int j = 0; j < kScanItems; ++j)
       if ((bits[j] >> c) & 1u) {
         const int64_t r = base + j;
         if (pos < cap) {
@@ -217,16 +187,16 @@ int tl_crops_check(const double* cell_x, int x_dim, const double* cell_y, int y_
   return TL_OK;
 }
 
-int64_t tl_crops_ws_words(int64_t n, int n_crops) { return tl_cdiv(n, kTile) * (int64_t)n_crops + 1; }
+int64_t tl_crops_ws_words(int64_t n, int n_crops) { return tl_cdiv(n, kScanTile) * (int64_t)n_crops + 1; }
 
 int tl_crops_count(const float* xyz, int64_t n, int n_crops, const float* centres, const double* rinv, double chunk_size, int32_t* counts,
                    int32_t* ws, tl_stream_t stream) {
   if (!xyz || !centres || !rinv || !counts || !ws || n <= 0 || n_crops <= 0 || n_crops > kMaxCrops) return TL_ERR_ARG;
   if (n > (int64_t)INT32_MAX / n_crops) return TL_ERR_ARG;             // row offsets of the whole batch are int32
-  const int64_t nb = tl_cdiv(n, kTile);
+  const int64_t nb = tl_cdiv(n, kScanTile);
   hipStream_t s = tl_s(stream);
   k_crop_partials<<<(unsigned)nb, 256, 0, s>>>(xyz, n, n_crops, centres, rinv, chunk_size / 2, ws, nb);
-  k_crop_scan<<<1, 256, 0, s>>>(ws, nb, n_crops, counts);
+  tl_launch_scan_parts(ws, nb, n_crops, counts, nullptr, s);       // crop-major: crop c's rows follow crop c-1's
   TL_CHECK_LAUNCH();
   return TL_OK;
 }
@@ -237,7 +207,7 @@ int tl_crops_extract(const float* xyz, const float* label, const float* feat, in
   if (!xyz || !label || (F > 0 && (!feat || !out_feat)) || !centres || !rinv || !ws || !out_xyz || !out_label || n <= 0 || F < 0 ||
       n_crops <= 0 || n_crops > kMaxCrops || capacity <= 0 || n > (int64_t)INT32_MAX / n_crops)
     return TL_ERR_ARG;
-  const int64_t nb = tl_cdiv(n, kTile);
+  const int64_t nb = tl_cdiv(n, kScanTile);
   k_crop_scatter<<<(unsigned)nb, 256, 0, tl_s(stream)>>>(xyz, label, feat, n, F, n_crops, centres, rinv, chunk_size / 2, ws, nb, capacity,
                                                           out_xyz, out_label, out_feat);
   TL_CHECK_LAUNCH();

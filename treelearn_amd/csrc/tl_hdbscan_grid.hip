@@ -13,7 +13,7 @@
 //     order: deterministic, and its weight multiset equals that of sklearn's Prim tree (every MST has the same weights); only the
 //     choice among equal-weight edges differs from Prim's insertion order.
 // The Prim form (tl_hdbscan_mst) stays: it reproduces sklearn's edge order exactly and is the test oracle of this file.
-#include "tl_common.h"
+#include "tl_scan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -90,47 +90,6 @@ __global__ void __launch_bounds__(kBlock) k_scatter(const float* __restrict__ xy
     const int p = start[c] + atomicAdd(&cursor[c], 1);
     sx[p] = (double)xy[2 * (int64_t)i]; sy[p] = (double)xy[2 * (int64_t)i + 1]; oid[p] = i;
   }
-}
-
-// exclusive scan of int[n] -> out[n + 1] (tile = 2048 items)
-constexpr int kItems = 8, kTile = kBlock * kItems;
-__device__ __forceinline__ int block_scan(int v, int* total) {
-  __shared__ int wsum[kBlock / 64];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int inc = v;
-  for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(inc, off); if (lane >= off) inc += t; }
-  if (lane == 63) wsum[wid] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-  for (int q = 0; q < kBlock / 64; ++q) { if (q < wid) base += wsum[q]; tot += wsum[q]; }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
-__global__ void __launch_bounds__(kBlock) k_scan1(const int* __restrict__ f, int64_t n, int* __restrict__ part) {
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
-  int s = 0;
-  for (int j = 0; j < kItems; ++j) if (base + j < n) s += f[base + j];
-  int tot; block_scan(s, &tot);
-  if (threadIdx.x == 0) part[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(kBlock) k_scan2(int* __restrict__ part, int64_t nb) {
-  int carry = 0;
-  for (int64_t b0 = 0; b0 < nb; b0 += kBlock) {
-    const int64_t i = b0 + threadIdx.x;
-    const int v = i < nb ? part[i] : 0;
-    int tot; const int ex = block_scan(v, &tot);
-    if (i < nb) part[i] = carry + ex;
-    carry += tot;
-  }
-}
-__global__ void __launch_bounds__(kBlock) k_scan3(const int* __restrict__ f, int64_t n, const int* __restrict__ part, int* __restrict__ out) {
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
-  int c[kItems]; int s = 0;
-  for (int j = 0; j < kItems; ++j) { c[j] = (base + j < n) ? f[base + j] : 0; s += c[j]; }
-  int tot; int ex = block_scan(s, &tot) + part[blockIdx.x];
-  for (int j = 0; j < kItems; ++j) { if (base + j < n) out[base + j] = ex; ex += c[j]; }
-  if (base <= n - 1 && n - 1 < base + kItems) out[n] = ex;        // the thread holding the last item also writes the total
 }
 
 // ---------------------------------------------------------------- node annotations
@@ -284,21 +243,6 @@ __global__ void __launch_bounds__(kBlock) k_core_big(const double* __restrict__ 
 }
 
 // ---------------------------------------------------------------- Boruvka
-__device__ __forceinline__ int find_root(int* parent, int x) {
-  while (true) {
-    const int p = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (p == x) return x;
-    x = p;
-  }
-}
-__device__ __forceinline__ bool unite(int* parent, int a, int b) {
-  while (true) {
-    a = find_root(parent, a); b = find_root(parent, b);
-    if (a == b) return false;
-    if (a < b) { const int t = a; a = b; b = t; }
-    if (atomicCAS(&parent[a], a, b) == a) return true;
-  }
-}
 __device__ __forceinline__ unsigned long long edge_key(int oa, int ob) {
   const unsigned lo = (unsigned)min(oa, ob), hi = (unsigned)max(oa, ob);
   return ((unsigned long long)lo << 32) | hi;
@@ -360,7 +304,7 @@ __global__ void __launch_bounds__(kBlock) k_merge(const double* __restrict__ pv,
     if (j < 0) continue;
     const int me = comp[p];
     if ((unsigned long long)__double_as_longlong(pv[p]) != comp_best[me] || edge_key(oid[p], oid[j]) != win[me]) continue;
-    if (unite(parent, p, j)) {                                   // fails only when the other component picked the same edge first
+    if (tl_unite(parent, p, j)) {                                   // fails only when the other component picked the same edge first
       const int e = atomicAdd(n_edges, 1);
       e_src[e] = min(oid[p], oid[j]); e_dst[e] = max(oid[p], oid[j]); e_w[e] = pv[p];
     }
@@ -369,7 +313,7 @@ __global__ void __launch_bounds__(kBlock) k_merge(const double* __restrict__ pv,
 __global__ void __launch_bounds__(kBlock) k_flatten(int* __restrict__ parent, int* __restrict__ comp, int n, unsigned long long* __restrict__ comp_best,
                                                     unsigned long long* __restrict__ win) {
   for (int p = blockIdx.x * kBlock + threadIdx.x; p < n; p += gridDim.x * kBlock) {
-    comp[p] = find_root(parent, p);
+    comp[p] = tl_find_root(parent, p);
     comp_best[p] = 0x7FF0000000000000ull;                        // +inf
     win[p] = kNone;
   }
@@ -393,7 +337,7 @@ inline Ws carve(void* ws, int64_t n, int L) {
   char* p = (char*)ws;
   Ws w;
   auto take = [&](int64_t b) { char* r = p; p += a16(b); return r; };
-  w.cell = (int*)take(n * 4); w.cnt = (int*)take(ncell * 4); w.start = (int*)take((ncell + 1) * 4); w.part = (int*)take((tl_cdiv(ncell, kTile) + 1) * 4);
+  w.cell = (int*)take(n * 4); w.cnt = (int*)take(ncell * 4); w.start = (int*)take((ncell + 1) * 4); w.part = (int*)take(tl_scan_parts_words(ncell) * 4);
   w.tag = (int*)take(nnode * 4); w.mincore = (float*)take(nnode * 4);
   w.oid = (int*)take(n * 4); w.comp = (int*)take(n * 4); w.parent = (int*)take(n * 4); w.pj = (int*)take(n * 4); w.n_edges = (int*)take(16);
   w.sx = (double*)take(n * 8); w.sy = (double*)take(n * 8); w.core = (double*)take(n * 8); w.pv = (double*)take(n * 8);
@@ -471,10 +415,7 @@ int tl_hdbscan_mst_grid(const float* xy, int64_t n, int min_samples, const TlHdb
   // sort by leaf cell
   if (hipMemsetAsync(w.cnt, 0, ncell * 4, s) != hipSuccess) return TL_ERR_LAUNCH;
   k_count<<<gp, kBlock, 0, s>>>(xy, ni, g, w.cell, w.cnt);
-  const int64_t nb = tl_cdiv(ncell, kTile);
-  k_scan1<<<(unsigned)nb, kBlock, 0, s>>>(w.cnt, ncell, w.part);
-  k_scan2<<<1, kBlock, 0, s>>>(w.part, nb);
-  k_scan3<<<(unsigned)nb, kBlock, 0, s>>>(w.cnt, ncell, w.part, w.start);
+  tl_launch_scan_i32(w.cnt, ncell, w.start, w.start + ncell, w.part, s);     // cell counts -> start[ncell + 1]
   if (hipMemsetAsync(w.cnt, 0, ncell * 4, s) != hipSuccess) return TL_ERR_LAUNCH;
   k_scatter<<<gp, kBlock, 0, s>>>(xy, ni, w.cell, w.start, w.cnt, w.sx, w.sy, w.oid);
   auto tags = [&](const int* comp) {

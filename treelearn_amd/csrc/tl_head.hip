@@ -1,4 +1,4 @@
-// Per-point heads (fused v2p gather + output_layer BN/ReLU + both 2-layer MLPs) and row compaction.
+// Per-point heads (fused v2p gather + output_layer BN/ReLU + both 2-layer MLPs).
 //
 // HBM-bound per-point work: one thread owns one point, holds its C-channel feature row in registers
 // and walks the (wave-uniform) weights through the scalar cache, so the [N,C] gathered tensor the
@@ -191,53 +191,6 @@ int launch_head(const void* feats, int64_t ld, int dtype, const int64_t* v2p, in
   return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
 }
 
-#ifndef TL_F16_BUILD
-// ---------------------------------------------------------------- stable row compaction
-constexpr int kItems = 8, kTile = 256 * kItems;
-
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* total) {
-  __shared__ uint32_t wsum[4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  uint32_t inc = v;
-  for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)inc, off); if (lane >= off) inc += t; }
-  if (lane == 63) wsum[wid] = inc;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-  for (int w = 0; w < 4; ++w) { if (w < wid) base += wsum[w]; tot += wsum[w]; }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
-
-__global__ void __launch_bounds__(256) k_mask_partials(const uint8_t* __restrict__ m, int64_t n, int32_t* __restrict__ part) {
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
-  uint32_t s = 0;
-  for (int j = 0; j < kItems; ++j) if (base + j < n) s += m[base + j] != 0;
-  uint32_t tot; block_scan(s, &tot);
-  if (threadIdx.x == 0) part[blockIdx.x] = (int32_t)tot;
-}
-__global__ void __launch_bounds__(256) k_mask_scan(int32_t* __restrict__ part, int64_t nb, int32_t* __restrict__ count) {
-  uint32_t carry = 0;
-  for (int64_t b0 = 0; b0 < nb; b0 += 256) {
-    const int64_t i = b0 + threadIdx.x;
-    const uint32_t v = i < nb ? (uint32_t)part[i] : 0u;
-    uint32_t tot; const uint32_t ex = block_scan(v, &tot);
-    if (i < nb) part[i] = (int32_t)(carry + ex);
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *count = (int32_t)carry;
-}
-__global__ void __launch_bounds__(256) k_mask_scatter(const float* __restrict__ in, int C, const uint8_t* __restrict__ m, int64_t n,
-                                                      const int32_t* __restrict__ part, float* __restrict__ out) {
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
-  uint32_t s = 0; bool keep[kItems];
-  for (int j = 0; j < kItems; ++j) { keep[j] = (base + j < n) && m[base + j] != 0; s += keep[j]; }
-  uint32_t tot; uint32_t pos = block_scan(s, &tot) + (uint32_t)part[blockIdx.x];
-  for (int j = 0; j < kItems; ++j) if (keep[j]) { for (int c = 0; c < C; ++c) out[(int64_t)pos * C + c] = in[(base + j) * C + c]; ++pos; }
-}
-
-#endif  // !TL_F16_BUILD
-
 }  // namespace
 
 extern "C" {
@@ -262,20 +215,5 @@ int tl_head_mlp(const void* feats, int64_t feats_ld, int dtype, int C, const int
   }
   return TL_ERR_UNSUPPORTED;
 }
-
-#ifndef TL_F16_BUILD
-int64_t tl_compact_ws_words(int64_t n) { return tl_cdiv(n, kTile) + 1; }
-
-int tl_compact_rows(const float* in, int C, const uint8_t* mask, int64_t n, float* out, int32_t* count, int32_t* ws, tl_stream_t stream) {
-  if (!in || !mask || !out || !count || !ws || C <= 0 || n <= 0) return TL_ERR_ARG;
-  const int64_t nb = tl_cdiv(n, kTile);
-  hipStream_t s = tl_s(stream);
-  k_mask_partials<<<(unsigned)nb, 256, 0, s>>>(mask, n, ws);
-  k_mask_scan<<<1, 256, 0, s>>>(ws, nb, count);
-  k_mask_scatter<<<(unsigned)nb, 256, 0, s>>>(in, C, mask, n, ws, out);
-  TL_CHECK_LAUNCH();
-  return TL_OK;
-}
-#endif  // !TL_F16_BUILD
 
 }  // extern "C"

@@ -15,29 +15,14 @@
 // double relative to itself, forms the sample covariance (n - 1), diagonalises it with cyclic Jacobi rotations and
 // returns 1 - |z component of the eigenvector of the smallest eigenvalue|.  Fewer than 3 neighbours -> NaN (the caller
 // replaces NaNs by the column mean like replace_nanfeatures, data_preparation.py:91-100).
-#include "tl_common.h"
+#include "tl_scan.h"
 
 namespace {
 
 constexpr int kBits = 21;
 constexpr int64_t kMask = (1ll << kBits) - 1;
-constexpr int kItems = 8, kTile = 256 * kItems;
 
 __device__ __forceinline__ double round2(double v) { return rint(v * 100.0) / 100.0; }          // np.round(x, 2) on float64
-
-__device__ __forceinline__ uint32_t block_scan3(uint32_t v, uint32_t* total) {
-  __shared__ uint32_t wsum[4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  uint32_t inc = v;
-  for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)inc, off); if (lane >= off) inc += t; }
-  if (lane == 63) wsum[wid] = inc;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-  for (int w = 0; w < 4; ++w) { if (w < wid) base += wsum[w]; tot += wsum[w]; }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
 
 __global__ void k_cell_keys(const double* __restrict__ xyz, int64_t n, double cell, double min_bound, int64_t b0, int64_t b1, int64_t b2,
                             int round_input, int64_t* __restrict__ keys, int32_t* __restrict__ err) {
@@ -55,33 +40,22 @@ __global__ void k_cell_keys(const double* __restrict__ xyz, int64_t n, double ce
 }
 
 __global__ void __launch_bounds__(256) k_head_partials(const int64_t* __restrict__ keys, int64_t n, int32_t* __restrict__ part) {
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
+  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
   uint32_t s = 0;
-  for (int j = 0; j < kItems; ++j) { const int64_t i = base + j; if (i < n) s += (i == 0 || keys[i] != keys[i - 1]); }
-  uint32_t tot; block_scan3(s, &tot);
+  for (int j = 0; j < kScanItems; ++j) { const int64_t i = base + j; if (i < n) s += (i == 0 || keys[i] != keys[i - 1]); }
+  uint32_t tot; tl_block_scan<4>(s, &tot);
   if (threadIdx.x == 0) part[blockIdx.x] = (int32_t)tot;
-}
-__global__ void __launch_bounds__(256) k_head_scan(int32_t* __restrict__ part, int64_t nb, int64_t* __restrict__ count) {
-  uint32_t carry = 0;
-  for (int64_t b0 = 0; b0 < nb; b0 += 256) {
-    const int64_t i = b0 + threadIdx.x;
-    const uint32_t v = i < nb ? (uint32_t)part[i] : 0u;
-    uint32_t tot; const uint32_t ex = block_scan3(v, &tot);
-    if (i < nb) part[i] = (int32_t)(carry + ex);
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *count = (int64_t)carry;
 }
 // one thread per voxel (segment of equal keys): in-order double sum, first index, trace
 template <bool kRoundF64>
 __global__ void __launch_bounds__(256) k_ds_reduce(const double* __restrict__ xyz, const int64_t* __restrict__ keys, const int64_t* __restrict__ perm,
                                                    int64_t n, const int32_t* __restrict__ part, float* __restrict__ out_xyz,
                                                    int64_t* __restrict__ first_idx, int64_t* __restrict__ point2vox) {
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
-  uint32_t s = 0; bool head[kItems];
-  for (int j = 0; j < kItems; ++j) { const int64_t i = base + j; head[j] = i < n && (i == 0 || keys[i] != keys[i - 1]); s += head[j]; }
-  uint32_t tot; int64_t vox = block_scan3(s, &tot) + (uint32_t)part[blockIdx.x];
-  for (int j = 0; j < kItems; ++j)
+  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+  uint32_t s = 0; bool head[kScanItems];
+  for (int j = 0; j < kScanItems; ++j) { const int64_t i = base + j; head[j] = i < n && (i == 0 || keys[i] != keys[i - 1]); s += head[j]; }
+  uint32_t tot; int64_t vox = tl_block_scan<4>(s, &tot) + (uint32_t)part[blockIdx.x];
+  for (int j = 0; j < kScanItems; ++j)
     if (head[j]) {
       const int64_t i = base + j, key = keys[i];
       double sx = 0.0, sy = 0.0, sz = 0.0; int64_t cnt = 0;
@@ -108,11 +82,11 @@ __global__ void __launch_bounds__(256) k_ds_reduce(const double* __restrict__ xy
 __global__ void __launch_bounds__(256) k_group_mean(const float* __restrict__ src, int C, const int64_t* __restrict__ keys,
                                                     const int64_t* __restrict__ perm, int64_t n, const int32_t* __restrict__ part,
                                                     double* __restrict__ mean, int64_t* __restrict__ first_idx) {
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
-  uint32_t s = 0; bool head[kItems];
-  for (int j = 0; j < kItems; ++j) { const int64_t i = base + j; head[j] = i < n && (i == 0 || keys[i] != keys[i - 1]); s += head[j]; }
-  uint32_t tot; int64_t grp = block_scan3(s, &tot) + (uint32_t)part[blockIdx.x];
-  for (int j = 0; j < kItems; ++j)
+  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+  uint32_t s = 0; bool head[kScanItems];
+  for (int j = 0; j < kScanItems; ++j) { const int64_t i = base + j; head[j] = i < n && (i == 0 || keys[i] != keys[i - 1]); s += head[j]; }
+  uint32_t tot; int64_t grp = tl_block_scan<4>(s, &tot) + (uint32_t)part[blockIdx.x];
+  for (int j = 0; j < kScanItems; ++j)
     if (head[j]) {
       const int64_t i = base + j, key = keys[i];
       int64_t cnt = 0;
@@ -207,15 +181,15 @@ int tl_cell_keys(const double* xyz, int64_t n, double cell, double min_bound, co
   return TL_OK;
 }
 
-int64_t tl_downsample_ws_words(int64_t n) { return tl_cdiv(n, kTile) + 1; }
+int64_t tl_downsample_ws_words(int64_t n) { return tl_scan_parts_words(n); }
 
 static int downsample_reduce(bool round_f64, const double* xyz, const int64_t* sorted_keys, const int64_t* perm, int64_t n, float* out_xyz,
                              int64_t* first_idx, int64_t* point2vox, int64_t* n_voxels, int32_t* ws, tl_stream_t stream) {
   if (!xyz || !sorted_keys || !perm || !out_xyz || !first_idx || !point2vox || !n_voxels || !ws || n <= 0) return TL_ERR_ARG;
-  const int64_t nb = tl_cdiv(n, kTile);
+  const int64_t nb = tl_cdiv(n, kScanTile);
   hipStream_t s = tl_s(stream);
   k_head_partials<<<(unsigned)nb, 256, 0, s>>>(sorted_keys, n, ws);
-  k_head_scan<<<1, 256, 0, s>>>(ws, nb, n_voxels);
+  tl_launch_scan_parts(ws, nb, 1, nullptr, n_voxels, s);
   if (round_f64) k_ds_reduce<true><<<(unsigned)nb, 256, 0, s>>>(xyz, sorted_keys, perm, n, ws, out_xyz, first_idx, point2vox);
   else k_ds_reduce<false><<<(unsigned)nb, 256, 0, s>>>(xyz, sorted_keys, perm, n, ws, out_xyz, first_idx, point2vox);
   TL_CHECK_LAUNCH();
@@ -235,10 +209,10 @@ int tl_downsample_reduce_r64(const double* xyz, const int64_t* sorted_keys, cons
 int tl_group_mean(const float* src, int64_t n, int C, const int64_t* sorted_keys, const int64_t* perm, double* mean, int64_t* first_idx,
                   int64_t* n_groups, int32_t* ws, tl_stream_t stream) {
   if (!src || !sorted_keys || !perm || !mean || !first_idx || !n_groups || !ws || n <= 0 || C <= 0) return TL_ERR_ARG;
-  const int64_t nb = tl_cdiv(n, kTile);
+  const int64_t nb = tl_cdiv(n, kScanTile);
   hipStream_t s = tl_s(stream);
   k_head_partials<<<(unsigned)nb, 256, 0, s>>>(sorted_keys, n, ws);
-  k_head_scan<<<1, 256, 0, s>>>(ws, nb, n_groups);
+  tl_launch_scan_parts(ws, nb, 1, nullptr, n_groups, s);
   k_group_mean<<<(unsigned)nb, 256, 0, s>>>(src, C, sorted_keys, perm, n, ws, mean, first_idx);
   TL_CHECK_LAUNCH();
   return TL_OK;

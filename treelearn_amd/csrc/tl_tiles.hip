@@ -8,25 +8,9 @@
 //   inner-square occupancy: float64 compares (numpy float32 array vs np.float64 scalars);
 //   centring: float64 subtraction of the float32-computed tile centre, stored as float32;
 //   masks_inner: inf-norm of the centred float32 xy <= inner_square_edge_length / 2.
-#include "tl_common.h"
+#include "tl_scan.h"
 
 namespace {
-
-constexpr int kItems = 8, kTile = 256 * kItems;
-
-__device__ __forceinline__ uint32_t block_scan2(uint32_t v, uint32_t* total) {
-  __shared__ uint32_t wsum[4];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  uint32_t inc = v;
-  for (int off = 1; off < 64; off <<= 1) { const uint32_t t = (uint32_t)__shfl_up((int)inc, off); if (lane >= off) inc += t; }
-  if (lane == 63) wsum[wid] = inc;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-  for (int w = 0; w < 4; ++w) { if (w < wid) base += wsum[w]; tot += wsum[w]; }
-  __syncthreads();
-  *total = tot;
-  return base + inc - v;
-}
 
 __device__ __forceinline__ bool in_outer(const tl_tile_box& b, float x, float y) {
   return x >= b.outer[0] && x <= b.outer[1] && y >= b.outer[2] && y <= b.outer[3];
@@ -39,41 +23,30 @@ __device__ __forceinline__ bool in_inner(const tl_tile_box& b, float x, float y)
 // per block: kept rows; rows inside the inner square are summed into count[1] (at most one atomic per wave)
 __global__ void __launch_bounds__(256) k_tile_partials(const float* __restrict__ xyz, int64_t n, tl_tile_box box, int32_t* __restrict__ part,
                                                        int32_t* __restrict__ count) {
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
+  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
   uint32_t s = 0, in = 0;
-  for (int j = 0; j < kItems; ++j)
+  for (int j = 0; j < kScanItems; ++j)
     if (base + j < n) {
       const float x = xyz[(base + j) * 3], y = xyz[(base + j) * 3 + 1];
       if (in_outer(box, x, y)) { ++s; in += in_inner(box, x, y); }
     }
-  uint32_t tot; block_scan2(s, &tot);
+  uint32_t tot; tl_block_scan<4>(s, &tot);
   if (threadIdx.x == 0) part[blockIdx.x] = (int32_t)tot;
-  uint32_t tin; block_scan2(in, &tin);
+  uint32_t tin; tl_block_scan<4>(in, &tin);
   if (threadIdx.x == 0 && tin) atomicAdd(&count[1], (int32_t)tin);
-}
-__global__ void __launch_bounds__(256) k_tile_scan(int32_t* __restrict__ part, int64_t nb, int32_t* __restrict__ count) {
-  uint32_t carry = 0;
-  for (int64_t b0 = 0; b0 < nb; b0 += 256) {
-    const int64_t i = b0 + threadIdx.x;
-    const uint32_t v = i < nb ? (uint32_t)part[i] : 0u;
-    uint32_t tot; const uint32_t ex = block_scan2(v, &tot);
-    if (i < nb) part[i] = (int32_t)(carry + ex);
-    carry += tot;
-  }
-  if (threadIdx.x == 0) count[0] = (int32_t)carry;
 }
 __global__ void __launch_bounds__(256) k_tile_scatter(const float* __restrict__ xyz, const float* __restrict__ label, const float* __restrict__ feat,
                                                       int64_t n, int F, tl_tile_box box, const int32_t* __restrict__ part,
                                                       float* __restrict__ coords, float* __restrict__ ofeat, int64_t* __restrict__ inst,
                                                       int64_t* __restrict__ sem, uint8_t* __restrict__ m_inner, uint8_t* __restrict__ m_sem) {
-  const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
-  uint32_t s = 0; bool keep[kItems];
-  for (int j = 0; j < kItems; ++j) {
+  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
+  uint32_t s = 0; bool keep[kScanItems];
+  for (int j = 0; j < kScanItems; ++j) {
     keep[j] = (base + j < n) && in_outer(box, xyz[(base + j) * 3], xyz[(base + j) * 3 + 1]);
     s += keep[j];
   }
-  uint32_t tot; int64_t pos = block_scan2(s, &tot) + (uint32_t)part[blockIdx.x];
-  for (int j = 0; j < kItems; ++j)
+  uint32_t tot; int64_t pos = tl_block_scan<4>(s, &tot) + (uint32_t)part[blockIdx.x];
+  for (int j = 0; j < kScanItems; ++j)
     if (keep[j]) {
       const int64_t r = base + j;
       const float cx = (float)((double)xyz[r * 3] - box.center[0]), cy = (float)((double)xyz[r * 3 + 1] - box.center[1]);
@@ -93,7 +66,7 @@ __global__ void __launch_bounds__(256) k_tile_scatter(const float* __restrict__ 
 
 extern "C" {
 
-int64_t tl_tile_crop_ws_words(int64_t n) { return tl_cdiv(n, kTile) + 1; }
+int64_t tl_tile_crop_ws_words(int64_t n) { return tl_scan_parts_words(n); }
 
 int tl_tile_crop(const float* xyz, const float* label, const float* feat, int64_t n, int F, const tl_tile_box* box, float* coords,
                  float* out_feat, int64_t* instance_labels, int64_t* semantic_labels, uint8_t* mask_inner, uint8_t* mask_sem,
@@ -101,11 +74,11 @@ int tl_tile_crop(const float* xyz, const float* label, const float* feat, int64_
   if (!xyz || !label || (F > 0 && (!feat || !out_feat)) || !box || !coords || !instance_labels || !semantic_labels || !mask_inner || !mask_sem ||
       !count || !ws || n <= 0 || F < 0)
     return TL_ERR_ARG;
-  const int64_t nb = tl_cdiv(n, kTile);
+  const int64_t nb = tl_cdiv(n, kScanTile);
   hipStream_t s = tl_s(stream);
   if (hipMemsetAsync(count, 0, 2 * sizeof(int32_t), s) != hipSuccess) return TL_ERR_LAUNCH;
   k_tile_partials<<<(unsigned)nb, 256, 0, s>>>(xyz, n, *box, ws, count);
-  k_tile_scan<<<1, 256, 0, s>>>(ws, nb, count);
+  tl_launch_scan_parts(ws, nb, 1, count, nullptr, s);
   k_tile_scatter<<<(unsigned)nb, 256, 0, s>>>(xyz, label, feat, n, F, *box, ws, coords, out_feat, instance_labels, semantic_labels, mask_inner, mask_sem);
   TL_CHECK_LAUNCH();
   return TL_OK;

@@ -6,7 +6,7 @@
 // order.  For a 40x40 m tile at 0.1 m the bitmap is 6 MB and the prefix 3 MB: both stay in the
 // 256 MB Infinity Cache (mostly in the 4 MB/XCD L2), so the 27 probes per voxel of the
 // submanifold rulebook never touch HBM and need neither hashing nor sorting.
-#include "tl_common.h"
+#include "tl_scan.h"
 
 namespace {
 
@@ -319,62 +319,10 @@ __global__ void __launch_bounds__(kBlock) k_bitmap_down(const uint64_t* __restri
 }
 
 // ---------------------------------------------------------------- popcount exclusive scan (3 passes)
-constexpr int kScanItems = 8;                       // words per thread
-constexpr int kScanTile = kBlock * kScanItems;      // words per block
 constexpr int kScanMaxLevels = 8;
 
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* total_out) {
-  __shared__ uint32_t wsum[kBlock / 64];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  uint32_t inc = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t t = (uint32_t)__shfl_up((int)inc, off);
-    if (lane >= off) inc += t;
-  }
-  if (lane == 63) wsum[wid] = inc;
-  __syncthreads();
-  uint32_t base = 0, tot = 0;
-  for (int w = 0; w < kBlock / 64; ++w) { if (w < wid) base += wsum[w]; tot += wsum[w]; }
-  __syncthreads();
-  *total_out = tot;
-  return base + inc - v;
-}
-
-__global__ void __launch_bounds__(kBlock) k_scan_partials(const uint64_t* __restrict__ bm, int64_t n, uint32_t* __restrict__ part) {
-  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-  uint32_t s = 0;
-  for (int j = 0; j < kScanItems; ++j) if (base + j < n) s += __popcll(bm[base + j]);
-  uint32_t tot;
-  block_exclusive_scan(s, &tot);
-  if (threadIdx.x == 0) part[blockIdx.x] = tot;
-}
-
-__global__ void __launch_bounds__(kBlock) k_scan_blocks(uint32_t* __restrict__ part, int64_t nb, uint32_t* __restrict__ total) {
-  uint32_t carry = 0;                               // single block walks the partials
-  for (int64_t base = 0; base < nb; base += kBlock) {
-    const int64_t i = base + threadIdx.x;
-    const uint32_t v = i < nb ? part[i] : 0;
-    uint32_t tot;
-    const uint32_t ex = block_exclusive_scan(v, &tot);
-    if (i < nb) part[i] = carry + ex;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
-
-__global__ void __launch_bounds__(kBlock) k_scan_final(const uint64_t* __restrict__ bm, int64_t n, const uint32_t* __restrict__ part,
-                                                       uint32_t* __restrict__ prefix) {
-  const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-  uint32_t c[kScanItems];
-  uint32_t s = 0;
-  for (int j = 0; j < kScanItems; ++j) { c[j] = (base + j < n) ? __popcll(bm[base + j]) : 0; s += c[j]; }
-  uint32_t tot;
-  uint32_t ex = block_exclusive_scan(s, &tot) + part[blockIdx.x];
-  for (int j = 0; j < kScanItems; ++j) { if (base + j < n) prefix[base + j] = ex; ex += c[j]; }
-}
-
 // The popcount scans of SEVERAL levels in one launch per pass (tl_pyramid_build: the big levels of the pyramid; their bitmaps are complete
-// before the first pass starts).  Workgroup b works on level l with first[l] <= b < first[l + 1]; the partials of a level are contiguous.
+// before the first pass starts; tl_bitmap_scan: one level).  Workgroup b works on level l with first[l] <= b < first[l + 1]; the partials of a level are contiguous.
 struct ScanPack {
   int nl;
   int first[kScanMaxLevels + 1];
@@ -394,7 +342,7 @@ __global__ void __launch_bounds__(kBlock) k_scan_partials_multi(const uint64_t* 
   uint32_t s = 0;
   for (int j = 0; j < kScanItems; ++j) if (base + j < n) s += __popcll(bm[base + j]);
   uint32_t tot;
-  block_exclusive_scan(s, &tot);
+  tl_block_scan<4>(s, &tot);
   if (threadIdx.x == 0) part[blockIdx.x] = tot;
 }
 __global__ void __launch_bounds__(kBlock) k_scan_blocks_multi(uint32_t* __restrict__ part, ScanPack p, uint32_t* __restrict__ totals) {
@@ -405,7 +353,7 @@ __global__ void __launch_bounds__(kBlock) k_scan_blocks_multi(uint32_t* __restri
       const int64_t i = base + threadIdx.x;
       const uint32_t v = i < nb ? part[lo + i] : 0;
       uint32_t tot;
-      const uint32_t ex = block_exclusive_scan(v, &tot);
+      const uint32_t ex = tl_block_scan<4>(v, &tot);
       if (i < nb) part[lo + i] = carry + ex;
       carry += tot;
     }
@@ -423,7 +371,7 @@ __global__ void __launch_bounds__(kBlock) k_scan_final_multi(const uint64_t* __r
   uint32_t s = 0;
   for (int j = 0; j < kScanItems; ++j) { c[j] = (base + j < n) ? __popcll(bm[base + j]) : 0; s += c[j]; }
   uint32_t tot;
-  uint32_t ex = block_exclusive_scan(s, &tot) + part[blockIdx.x];
+  uint32_t ex = tl_block_scan<4>(s, &tot) + part[blockIdx.x];
   for (int j = 0; j < kScanItems; ++j) { if (base + j < n) prefix[base + j] = ex; ex += c[j]; }
 }
 
@@ -765,15 +713,16 @@ int tl_bitmap_down(const uint64_t* fine, const int32_t fdims[4], const int32_t o
   return TL_OK;
 }
 
-int64_t tl_scan_ws_words(int64_t nwords) { return tl_cdiv(nwords, kScanTile) + 1; }
+int64_t tl_scan_ws_words(int64_t nwords) { return tl_scan_parts_words(nwords); }
 
 int tl_bitmap_scan(const uint64_t* bitmap, int64_t nwords, uint32_t* prefix, uint32_t* total, uint32_t* ws, tl_stream_t stream) {
   if (!bitmap || !prefix || !total || !ws || nwords <= 0) return TL_ERR_ARG;
-  const int64_t nb = tl_cdiv(nwords, kScanTile);
+  ScanPack sp;                                         // one level of the several-level scan
+  sp.nl = 1; sp.first[0] = 0; sp.first[1] = (int)tl_cdiv(nwords, kScanTile); sp.off[0] = 0; sp.nw[0] = nwords;
   hipStream_t s = tl_s(stream);
-  k_scan_partials<<<(unsigned)nb, kBlock, 0, s>>>(bitmap, nwords, ws);
-  k_scan_blocks<<<1, kBlock, 0, s>>>(ws, nb, total);
-  k_scan_final<<<(unsigned)nb, kBlock, 0, s>>>(bitmap, nwords, ws, prefix);
+  k_scan_partials_multi<<<(unsigned)sp.first[1], kBlock, 0, s>>>(bitmap, sp, ws);
+  k_scan_blocks_multi<<<1, kBlock, 0, s>>>(ws, sp, total);
+  k_scan_final_multi<<<(unsigned)sp.first[1], kBlock, 0, s>>>(bitmap, sp, ws, prefix);
   TL_CHECK_LAUNCH();
   return TL_OK;
 }
@@ -887,7 +836,7 @@ int tl_pyramid_build(const int32_t* pcoords, int64_t N, const int32_t dims0[4], 
     k_bytes_to_bits<<<tl_grid(nw0, kBlock), kBlock, 0, s>>>(bytes, nw0, bitmaps);
   }
   // the big levels: every bitmap first (one down-sampling launch per level), then ONE three-pass popcount scan over all of them (eleven small
-  // dependent launches were five microseconds each on the path to the second read-back; the per-level entry points above keep the plain form)
+  // dependent launches were five microseconds each on the path to the second read-back; tl_bitmap_scan is the same scan with one level)
   int l = 0;
   ScanPack sp;
   sp.first[0] = 0;
