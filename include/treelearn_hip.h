@@ -690,6 +690,38 @@ int tl_tree_ground(const double* sorted_xyz, int64_t n, const int64_t* start, in
                    double slice_height, double slice_thickness, double dbh_max_radius, int64_t dbh_min_points, double* ground_table,
                    int64_t* ground_n, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ LAS point records (csrc/tl_las.hip)
+ * The record passes of the LAS reader and writer (treelearn_amd/util/las.py parses and writes the headers on the host).  The layout is
+ * the ASPRS one and the rules are restated in numpy in tests/las_restatement.py; all arithmetic is f64 in plain operators, no fma
+ * contraction.
+ * tl_las_decode: records u8[n * record_length] (device, base aligned to 16), little endian, i32 X Y Z at bytes 0, 4, 8.  Writes rows
+ *   first_row .. first_row + n - 1 of out f64[*, out_cols]: x = X * scale[0] + offset[0] (a multiply, then an add), the same for y, z.
+ *   out_cols = 4 needs a treeID dimension (tree_id_offset = its byte offset in the record, tree_id_type = 1 .. 10 as the extra-bytes
+ *   VLR numbers them: u8 i8 u16 i16 u32 i32 u64 i64 f32 f64) and the classification (the byte at class_offset, and-ed with class_mask:
+ *   15 / 0x1f for point formats 0-5, 16 / 0xff for 6-10).  With t = treeID widened to f64 and c the class: label = 0 where c is 1 or
+ *   2, else t where t != 0, else -1.  out_cols = 3 takes tree_id_type = 0 and ignores the other three.  `path`: 0 = the library's
+ *   choice, 1 = plain (one lane per record, byte loads), 2 = staged (256 records through LDS with 16-byte loads; TL_ERR_UNSUPPORTED
+ *   for a record longer than 128 bytes).  Both give the same bits.
+ * tl_las_encode: coords f32 or f64 by dtype_f64, n_src rows of stride ld >= 3 elements, labels i64[n_src]; output row j takes source
+ *   row order[j] (i64[n]; NULL: j, and n = n_src).  records u8[n * 38] (base aligned to 16): point format 3 + u32 treeID, X =
+ *   rint((x - offset) / scale) (subtract, divide, round half to even), intensity 0, return byte 0x09, classification 2 for label 0 and
+ *   4 otherwise, scan angle / user data / source 0, GPS time 0.0, RGB = 257 * the three low bytes of h (black for label 0), where
+ *   h = (u32)label * 2654435761, h ^= h >> 15, h *= 2246822519, h ^= h >> 13 (mod 2^32), treeID = the low 32 bits of the label.
+ *   A row whose coordinate is not finite, whose rint leaves [-2^31, 2^31 - 1] or whose order entry is outside 0 .. n_src - 1 gets an
+ *   all-zero record and sets *err (device, 0 otherwise): the caller raises and writes no file.  extremes i32[n_seg, 6] = min X, min Y,
+ *   min Z, max X, max Y, max Z of the written rows of each segment (integer atomics: exact for any order; INT32_MAX x 3, INT32_MIN x 3
+ *   for a segment without one).  seg_start i64[n_seg + 1] ascending with seg_start[0] = 0 and seg_start[n_seg] = n: segment s holds
+ *   output rows seg_start[s] .. seg_start[s + 1] - 1; NULL with n_seg = 1: the whole cloud.
+ * A null or misaligned pointer, a negative size, record_length outside 20 .. 65535, a field outside the record, out_cols other than 3
+ * or 4, a scale that is not positive and finite (encode), an unknown path: TL_ERR_ARG, nothing launched.  n = 0: TL_OK (encode still
+ * resets err and extremes). */
+int tl_las_decode(const uint8_t* records, int64_t n, int32_t record_length, int32_t class_offset, int32_t class_mask, int32_t tree_id_offset,
+                  int32_t tree_id_type, const double scale[3], const double offset[3], double* out, int32_t out_cols, int64_t first_row,
+                  int32_t path, tl_stream_t stream);
+int tl_las_encode(const void* coords, int dtype_f64, int64_t ld, int64_t n_src, const int64_t* labels, const int64_t* order, int64_t n,
+                  const double scale[3], const double offset[3], const int64_t* seg_start, int64_t n_seg, uint8_t* records, int32_t* err,
+                  int32_t* extremes, tl_stream_t stream);
+
 /* ------------------------------------------------------------------ validation metrics of a training run (csrc/tl_train_eval.hip)
  * Replaces `pointwise_eval` (tools/training/train.py:89-102) and the per-tile lists `validate` (:61-86) concatenates for it: called once
  * per validation tile, it ADDS that tile's share to a running state and keeps nothing per point.

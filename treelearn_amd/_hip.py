@@ -184,6 +184,8 @@ PROTOTYPES = {
     "tl_dtm_fill": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "tl_dtm_sample": (_i32, [_vp, _i32, _i64, _i64, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "tl_tree_ground": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _c.c_double, _c.c_double, _c.c_double, _i64, _vp, _vp, _vp]),
+    "tl_las_decode": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _c.c_double * 3, _c.c_double * 3, _vp, _i32, _i64, _i32, _vp]),
+    "tl_las_encode": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _i64, _c.c_double * 3, _c.c_double * 3, _vp, _i64, _vp, _vp, _vp, _vp]),
     "tl_pointwise_eval_ws_bytes": (_i64, [_i64]),
     "tl_pointwise_eval": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "tl_point_jitter": (_i32, [_vp, _i64, _c.c_uint64, _vp]),

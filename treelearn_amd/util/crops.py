@@ -364,7 +364,7 @@ def _number(s):
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser("python -m treelearn_amd.util.crops", description="generate random training crops from labelled forests")
-    ap.add_argument("--base-dir", required=True, help="directory holding forests/ (npy / npz / txt, N x 4 with labels)")
+    ap.add_argument("--base-dir", required=True, help="directory holding forests/ (npy / npz / txt / las, N x 4 with labels)")
     ap.add_argument("--seed", type=int, default=0)
     for k in ("n_samples_total", "chunk_size", "occupancy_res", "n_points_to_calculate_occupancy", "how_far_fill", "min_percent_occupied_fill",
               "min_percent_occupied_choose", "voxel_size", "search_radius_features"):

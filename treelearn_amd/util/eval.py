@@ -449,6 +449,17 @@ def load_points(path):
     return data
 
 
+def _load_labelled(path):
+    """load_points, and .las / .laz through util.las.read_las (a file without a treeID dimension has no label column and is refused)."""
+    if not path.lower().endswith((".las", ".laz")):
+        return load_points(path)
+    from .las import read_las
+    data = read_las(path)
+    if data.shape[1] != 4:
+        raise ValueError(f"{path}: expected N x 4 (x y z label), got {data.shape}: the file has no treeID dimension")
+    return data
+
+
 HEADLINE = (("Completeness", "detection_results", "completeness"), ("Omission Error Rate", "detection_results", "omission_error_rate"),
             ("Commission Error Rate", "detection_results", "commission_error_rate"), ("F1 Score", "detection_results", "f1_score"),
             ("Precision", "segmentation_results", "precision"), ("Recall", "segmentation_results", "recall"),
@@ -476,11 +487,11 @@ def flatten_results(results, propagated=None):
 
 def main(argv=None):
     ap = argparse.ArgumentParser("python -m treelearn_amd.util.eval", description="score a segmented forest against ground truth")
-    ap.add_argument("--gt", required=True, help="ground truth: .npy / .npz / .txt, N x 4 (x y z label)")
-    ap.add_argument("--pred", required=True, help="prediction: .npy / .npz / .txt, M x 4 (x y z label)")
+    ap.add_argument("--gt", required=True, help="ground truth: .npy / .npz / .txt / .las, N x 4 (x y z label)")
+    ap.add_argument("--pred", required=True, help="prediction: .npy / .npz / .txt / .las, M x 4 (x y z label)")
     ap.add_argument("--out", default=None, help="write the results dict (flattened) to this .npz")
     a = ap.parse_args(argv)
-    gt, pr = load_points(a.gt), load_points(a.pred)
+    gt, pr = _load_labelled(a.gt), _load_labelled(a.pred)
     res, prop = evaluate_forest(gt[:, :3], gt[:, 3], pr[:, :3], pr[:, 3], frames=False)
     for title, sec, key in HEADLINE:
         print(f"{title}: {res[sec][key]}%")

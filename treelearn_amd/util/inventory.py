@@ -1,7 +1,7 @@
 """Per-tree inventory of a segmented forest on the device: where each tree stands, how tall it is, its stem diameter at breast height
 (DBH) and how much ground its crown covers.
 
-    python -m treelearn_amd.util.inventory --forest labelled.npy|npz|txt --out trees.csv [--slice-height 1.3 ...]
+    python -m treelearn_amd.util.inventory --forest labelled.npy|npz|txt|las --out trees.csv [--slice-height 1.3 ...]
 
 The semantics are the project's own; tests/inventory_restatement.py states them in numpy float64.  Trees are the labels 1..T with
 T = max(label); labels <= 0 are ignored; a label in 1..T without rows is a tree of n_points = 0 with NaN in every float column.
@@ -261,7 +261,7 @@ def params_of(a):
 def main(argv=None):
     import os
     ap = argparse.ArgumentParser("python -m treelearn_amd.util.inventory", description="per-tree inventory (position, height, DBH, crown) of a labelled cloud")
-    ap.add_argument("--forest", required=True, help="labelled cloud: .npy / .npz / .txt, N x 4 (x y z label)")
+    ap.add_argument("--forest", required=True, help="labelled cloud: .npy / .npz / .txt / .las, N x 4 (x y z label)")
     ap.add_argument("--out", required=True, help="CSV to write")
     add_arguments(ap)
     ap.add_argument("--terrain", action="store_true", help="add the ground columns: terrain from the label-0 rows, height and DBH from the ground")

@@ -1,7 +1,7 @@
 """Segment a whole forest: the reference's `run_treelearn_pipeline` (tools/pipeline/pipeline.py:21-199) on the device, from one cloud
 to a segmented forest and one file per tree.
 
-    python -m treelearn_amd.util.segment --forest F.npy|npz|txt --weights model.pth --out DIR [...]
+    python -m treelearn_amd.util.segment --forest F.npy|npz|txt|las --weights model.pth --out DIR [...]
 
   segment_forest         <- pipeline.py:40-187 (centre, plot preparation, tile loop, ensemble, grouping, k-NN fill, then below)
   segment_from_pointwise <- pipeline.py:78-81,133-187 (outer-buffer removal, edge-tree categories, predictions back to the input cloud)
@@ -232,20 +232,21 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
 
 # ------------------------------------------------------------------------------------------------ files
 def check_formats(save_formats):
-    """Raise before any GPU work if a format is unknown or needs a module that is not installed (las / laz: laspy)."""
+    """Raise before any GPU work if a format is unknown or needs a module that is not installed (laz: laspy; las is written natively)."""
     for f in save_formats:
         if f not in SAVE_FORMATS:
             raise ValueError(f"unknown save format {f!r}; expected one of {SAVE_FORMATS}")
-        if f in ("las", "laz"):
+        if f == "laz":
             try:
                 import laspy  # noqa: F401
             except ImportError as e:
-                raise ImportError(f"save format {f!r} needs the 'laspy' module, which is not installed (use npz, npy or txt)") from e
+                raise ImportError(f"save format {f!r} needs the 'laspy' module, which is not installed (use las, npz, npy or txt)") from e
 
 
 def save_data(data, save_format, save_name, save_folder, use_offset=True):
-    """data N x 4 (x y z label) -> save_folder/save_name.<format> (util/pipeline.py:339-392's file contents for npy / npz / txt; las / laz
-    through laspy: point format 3, scale 1 mm, treeID extra dimension, classification 2 for label 0 and 4 otherwise)."""
+    """data N x 4 (x y z label) -> save_folder/save_name.<format> (util/pipeline.py:339-392's file contents for npy / npz / txt; las
+    through util.las.write_las, encoded on the device, and laz through laspy: point format 3, scale 1 mm, treeID extra dimension,
+    classification 2 for label 0 and 4 otherwise)."""
     path = os.path.join(save_folder, f"{save_name}.{save_format}")
     if save_format == "npy":
         np.save(path, data)
@@ -253,7 +254,10 @@ def save_data(data, save_format, save_name, save_folder, use_offset=True):
         np.savez_compressed(path, points=data[:, :3], labels=data[:, 3])
     elif save_format == "txt":
         np.savetxt(path, data)
-    elif save_format in ("las", "laz"):
+    elif save_format == "las":
+        from .las import write_las
+        write_las(path, data[:, :3], data[:, 3], use_offset=use_offset)
+    elif save_format == "laz":
         import laspy
         header = laspy.LasHeader(version="1.2", point_format=3)
         header.offsets = data[:, :3].mean(0) if (use_offset and len(data)) else np.zeros(3)
@@ -292,16 +296,28 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
             lab = lab.cuda()
         sl, order = torch.sort(lab, stable=True)                          # one sort instead of a mask per tree
         ids, counts = torch.unique_consecutive(sl, return_counts=True)
-        order, ids, counts = order.cpu().numpy(), ids.cpu().numpy(), counts.cpu().numpy()
         cats = np.asarray(result["categories"])
-        at = 0
-        for i, n in zip(ids.tolist(), counts.tolist()):
-            rows = order[at:at + n]; at += n
-            d = np.hstack([c0[rows], np.full((n, 1), float(i))])
+        ids, counts = ids.cpu().numpy(), counts.cpu().numpy()
+
+        def tree_dir(i):
+            """Where label i's file goes, or None for a label without a category."""
             if i == NON_TREES_LABEL_IN_GROUPING:
-                save_data(d, save_formats[0], "non_trees", trees_dir, use_offset=False)
-            elif 1 <= i <= len(cats):
-                save_data(d, save_formats[0], str(int(i)), os.path.join(trees_dir, CATEGORIES[int(cats[i - 1])]), use_offset=False)
+                return trees_dir
+            return os.path.join(trees_dir, CATEGORIES[int(cats[i - 1])]) if 1 <= i <= len(cats) else None
+
+        if save_formats[0] == "las":                                     # one encode in label order: every tree's file body is a byte range of it
+            from .las import write_las_segments
+            names = [("non_trees" if i == NON_TREES_LABEL_IN_GROUPING else str(int(i)), tree_dir(i)) for i in ids.tolist()]
+            write_las_segments([None if d is None else os.path.join(d, f"{n}.las") for n, d in names], c0, lab, order,
+                               np.concatenate([[0], np.cumsum(counts)]))
+        else:
+            order = order.cpu().numpy()
+            at = 0
+            for i, n in zip(ids.tolist(), counts.tolist()):
+                rows = order[at:at + n]; at += n
+                d = np.hstack([c0[rows], np.full((n, 1), float(i))])
+                if tree_dir(i) is not None:
+                    save_data(d, save_formats[0], "non_trees" if i == NON_TREES_LABEL_IN_GROUPING else str(int(i)), tree_dir(i), use_offset=False)
     if "inventory" in result:
         from .inventory import write_inventory
         os.makedirs(out_dir, exist_ok=True)
@@ -325,7 +341,11 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
 
 # ------------------------------------------------------------------------------------------------ command line
 def load_forest(path):
-    """N x 3 or N x 4 float64 from .npy, .npz ('points' [+ 'labels']) or whitespace-separated .txt."""
+    """N x 3 or N x 4 float64 from .npy, .npz ('points' [+ 'labels']), whitespace-separated .txt, or .las / .laz (util.las.read_las:
+    x y z, and the label column when the file has a treeID dimension)."""
+    if path.lower().endswith((".las", ".laz")):
+        from .las import read_las
+        return read_las(path)
     from .eval import _read_points
     data = _read_points(path)
     if data.ndim != 2 or data.shape[1] not in (3, 4):
@@ -340,7 +360,7 @@ def sample_generator_of(a):
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser("python -m treelearn_amd.util.segment", description="segment a forest point cloud into trees")
-    ap.add_argument("--forest", required=True, help="input cloud: .npy / .npz / .txt, N x 3 or N x 4")
+    ap.add_argument("--forest", required=True, help="input cloud: .npy / .npz / .txt / .las, N x 3 or N x 4")
     ap.add_argument("--weights", required=True, help="model checkpoint (.pth with a 'net' state dict)")
     ap.add_argument("--out", required=True, help="results directory")
     ap.add_argument("--voxel-size", type=float, default=SAMPLE_CFG["voxel_size"])

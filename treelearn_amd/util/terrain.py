@@ -1,7 +1,7 @@
 """Terrain model of a segmented forest on the device: a raster of ground heights (DTM), the ground under any point, height above
 ground per point, and -- through util.inventory -- tree height and DBH measured from the ground.
 
-    python -m treelearn_amd.util.terrain --forest cloud.npy|npz|txt --out dtm.npz [--hag hag.npy] [--cell 0.5 ...]
+    python -m treelearn_amd.util.terrain --forest cloud.npy|npz|txt|las --out dtm.npz [--hag hag.npy] [--cell 0.5 ...]
 
 The semantics are the project's own; tests/terrain_restatement.py states them in numpy float64.
 
@@ -248,7 +248,7 @@ def params_of(a):
 def main(argv=None):
     import os
     ap = argparse.ArgumentParser("python -m treelearn_amd.util.terrain", description="terrain model (DTM) and height above ground of a cloud")
-    ap.add_argument("--forest", required=True, help="cloud: .npy / .npz / .txt, N x 3 (x y z) or N x 4 (x y z label; label 0 = ground candidates)")
+    ap.add_argument("--forest", required=True, help="cloud: .npy / .npz / .txt / .las, N x 3 (x y z) or N x 4 (x y z label; label 0 = ground candidates)")
     ap.add_argument("--out", required=True, help=".npz to write: x0, y0, cell, z, state, n_candidates")
     ap.add_argument("--hag", default=None, help=".npy to write: N x 4, x y z height_above_ground in the input's frame")
     add_arguments(ap)

@@ -283,7 +283,7 @@ def write_tiles(forest_path, sample_cfg=None, logger=None):
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser("python -m treelearn_amd.util.tiles", description="write the validation tiles of a labelled forest")
-    ap.add_argument("--forest", required=True, help="labelled cloud <base>/<dir>/<plot>.npy|npz|txt, N x 4; tiles go to <base>/tiles")
+    ap.add_argument("--forest", required=True, help="labelled cloud <base>/<dir>/<plot>.npy|npz|txt|las, N x 4; tiles go to <base>/tiles")
     ap.add_argument("--voxel-size", type=float, default=VAL_CFG["voxel_size"])
     ap.add_argument("--search-radius-features", type=float, default=VAL_CFG["search_radius_features"])
     ap.add_argument("--inner-edge", type=float, default=VAL_CFG["inner_edge"])
