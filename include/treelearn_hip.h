@@ -396,8 +396,9 @@ int tl_linear_small_f32(const void* x, int64_t x_ld, int dtype, const void* w, i
 /* Voxel -> point feature gather and its gradient (tree_learn.py:98 `output.features[v2p_map]`; tools/training/train.py:40):
  *   tl_gather_rows     : out[p, :] = in[idx[p], :] for p < N (idx < 0 counts from the end like torch indexing; in [n_rows, C]);
  *   tl_scatter_add_rows: gin[v, :] = sum over the points p with idx[p] == v of g[p, :], added in ascending p in fp32; `order` i64[N] =
- *                        the STABLE argsort of idx, sorted_idx = idx[order]; gin [n_rows, C] contiguous, fully written (rows without a
- *                        point are zero).  Deterministic, no atomics.  C * sizeof(elem) % 16 == 0, 16-B aligned rows. */
+ *                        the STABLE argsort of idx, sorted_idx = idx[order], idx NORMALISED to 0 <= idx < n_rows before the sort
+ *                        (points are grouped by equal sorted values: -1 and n_rows - 1 would be two groups writing one row); gin
+ *                        [n_rows, C] contiguous, fully written (rows without a point are zero).  Deterministic, no atomics.  C * sizeof(elem) % 16 == 0, 16-B aligned rows. */
 int tl_gather_rows(const void* in, int64_t in_ld, int dtype, int C, int64_t n_rows, const int64_t* idx, int64_t N, void* out, int64_t out_ld, tl_stream_t stream);
 int tl_scatter_add_rows(const void* g, int64_t g_ld, int dtype, int C, const int64_t* order, const int64_t* sorted_idx, int64_t N, int64_t n_rows, void* gin,
                         int64_t gin_ld, tl_stream_t stream);

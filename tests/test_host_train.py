@@ -188,3 +188,45 @@ def test_restatement_on_a_hand_worked_example():
     assert r["acc"] == pytest.approx(0.6) and r["offset_mae"] == pytest.approx((5.0 + 0.0 + 3.0) / 3)
     r = R.pointwise_eval(logits, off, torch.ones(5, dtype=torch.long), lab)
     assert r["n_off"] == 0 and r["offset_mae"] == 0.0
+
+
+def test_batchnorm_entry_points_refuse_bad_views_before_any_launch():
+    """Contracts checked on the host, so no GPU is needed: the wrappers refuse an operand with a column stride (a transposed view would be
+    read as if its columns were adjacent), and the C entry points refuse ld % 4, C % 4 and C > 1024 before they launch anything."""
+    from treelearn_amd import _hip, ops
+    x = torch.zeros((40, 32)); xt = torch.zeros((32, 40)).t(); wide = torch.zeros((40, 64))[:, ::2]
+    gamma = torch.ones(32); st = torch.zeros((4, 32)); parts = torch.zeros((4, 2, 32), dtype=torch.float64)
+    for bad in (xt, wide):
+        with pytest.raises(ValueError):
+            ops.bn_train_stats(bad, gamma, gamma, 1e-4, 0.1)
+        with pytest.raises(ValueError):
+            ops.bn_train_bwd(bad, x, st, True)
+        with pytest.raises(ValueError):
+            ops.bn_train_bwd(x, bad, st, True)
+        with pytest.raises(ValueError):
+            ops.bn_train_bwd(x, x, st, True, dx_add=bad)
+        with pytest.raises(ValueError):
+            ops.bn_train_bwd_from_parts(bad, x, st, parts, 4)
+        with pytest.raises(ValueError):
+            ops.bn_train_bwd_from_parts(x, bad, st, parts, 4)
+        with pytest.raises(ValueError):
+            ops.bn_train_bwd_from_parts(x, x, st, parts, 4, dx_add=bad)
+        with pytest.raises(ValueError):
+            ops.bn_train_bwd_from_parts(x, x, st, parts, 4, dx=bad)
+        with pytest.raises(ValueError):
+            ops.column_sum(bad)
+    lib = _hip.lib()
+    buf = (ctypes.c_double * 8192)()
+    p = ctypes.addressof(buf)
+    stats = lambda ld, n, C: lib.tl_bn_train_stats(p, ld, n, C, _hip.TL_F32, p, p, 1e-4, 0.1, p, p, p, p, p, None, None, None, None)      # noqa: E731
+    bwd = lambda ld, dld, xld, ald, C: lib.tl_bn_train_bwd(p, ld, _hip.TL_F32, p, dld, _hip.TL_F32, 16, C, p, p, p, p, 1, p, p, p, p, xld,       # noqa: E731
+                                                           p if ald else None, ald, None)
+    assert stats(10, 16, 8) == _hip.TL_ERR_ARG and stats(8, 16, 6) == _hip.TL_ERR_ARG and stats(1028, 16, 1028) == _hip.TL_ERR_ARG
+    assert stats(8, 0, 8) == _hip.TL_ERR_ARG
+    assert bwd(10, 8, 8, 0, 8) == _hip.TL_ERR_ARG and bwd(8, 10, 8, 0, 8) == _hip.TL_ERR_ARG and bwd(8, 8, 10, 0, 8) == _hip.TL_ERR_ARG
+    assert bwd(8, 8, 8, 10, 8) == _hip.TL_ERR_ARG and bwd(8, 8, 8, 0, 6) == _hip.TL_ERR_ARG and bwd(1028, 1028, 1028, 0, 1028) == _hip.TL_ERR_ARG
+    assert lib.tl_bn_ws_doubles(16, 6) == 0 and lib.tl_bn_ws_doubles(16, 1028) == 0 and lib.tl_bn_ws_doubles(16, 8) == 16
+    # mixed 16-bit types: one 16-bit type per call
+    assert lib.tl_bn_train_bwd(p, 8, _hip.TL_BF16, p, 8, _hip.TL_F16, 16, 8, p, p, p, p, 1, p, p, p, p, 8, None, 0, None) == _hip.TL_ERR_ARG
+    assert lib.tl_bn_train_bwd(p, 8, _hip.TL_F16, p, 8, _hip.TL_BF16, 16, 8, p, p, p, p, 1, p, p, p, p, 8, None, 0, None) == _hip.TL_ERR_ARG
+

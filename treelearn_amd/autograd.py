@@ -383,11 +383,13 @@ class _BiasAddFn(torch.autograd.Function):
             # left-over rows); ATen's dim-0 reduction of a [3.7 M, 3] matrix takes 0.6 ms
             r = 4 // math.gcd(C, 4)
             m = n - n % r
-            db = ops.column_sum(g[:m].view(m // r, r * C)).view(r, C).sum(0)
+            # (the r partial rows are added in fp64 and rounded once: each is far larger than a sum that cancels)
+            db = ops.column_sum64(g[:m].view(m // r, r * C)).view(r, C).sum(0)
             if m < n:
-                db = db + g[m:].float().sum(0)
+                db = db + g[m:].sum(0, dtype=torch.float64)
+            db = db.float()
         else:
-            db = g.float().sum(0)
+            db = g.sum(0, dtype=torch.float64).float()
         return g, db
 
 
@@ -403,7 +405,7 @@ def fusable_bn(module, x):
 
 class _GatherRowsFn(torch.autograd.Function):
     """point_feats = voxel_feats[v2p] (reference tree_learn.py:98) on tl_gather_rows; backward = tl_scatter_add_rows over the stable argsort
-    of v2p (cached on the geometry object: one sort per batch), deterministic."""
+    of v2p with negative indices folded to row numbers first (cached on the geometry object: one sort per batch), deterministic."""
 
     @staticmethod
     def forward(ctx, feats, idx, cache):
@@ -420,7 +422,8 @@ class _GatherRowsFn(torch.autograd.Function):
             g = g.contiguous()
         srt = ctx.cache.get("v2p_sort") if ctx.cache is not None else None
         if srt is None:
-            sidx, order = torch.sort(idx, stable=True)
+            # normalised BEFORE the sort: tl_scatter_add_rows groups equal sorted values, and -1 and n_rows - 1 are one row
+            sidx, order = torch.sort(torch.where(idx < 0, idx + ctx.n_rows, idx), stable=True)
             srt = (order, sidx)
             if ctx.cache is not None:
                 ctx.cache["v2p_sort"] = srt

@@ -4,6 +4,8 @@
 //   tl_gather_rows     : out[p] = in[idx[p]]                                   (idx < 0 counts from the end, as torch indexing does)
 //   tl_scatter_add_rows: gin[v] = sum of g[p] over the points p of voxel v, added in ascending p (the caller passes the stable argsort
 //                        of idx once per batch), fp32 accumulation, every voxel row written exactly once -- deterministic, no atomics.
+//                        sorted_idx must be NORMALISED (0 <= v < n_rows) before the sort: points are grouped by equal sorted values, so
+//                        -1 next to n_rows - 1 would make two groups that both write the last row.
 #include "tl_conv_internal.h"
 #include "tl_f16_train.h"
 

@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(kWaves * 64) k_wgrad(const void* __restrict__ 
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(x), 0, (int)min((int64_t)0x7FFFFFFF, n_in * x_ld * EB), 0x00020000);
   const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(g), 0, (int)min((int64_t)0x7FFFFFFF, n_out * g_ld * EB), 0x00020000);
   auto ld = [&](const __amdgpu_buffer_rsrc_t& r, unsigned off) __attribute__((always_inline)) -> float {
-    if constexpr (BF16) return __uint_as_float((uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(r, (int)off, 0, 0) << 16);
+    if constexpr (BF16) return bf16_lo((uint32_t)(uint16_t)__builtin_amdgcn_raw_buffer_load_b16(r, (int)off, 0, 0));     // (the unit's 16-bit type: IEEE half in the f16 build)
     else return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
   };
   unsigned offx[NBI], offg[NBO];                 // per-lane channel offsets (bytes), out of range -> 0xFFFFFFFF (reads as 0)

@@ -270,10 +270,21 @@ def affine_relu(x, scale, shift, relu, out_dtype=None):
     return y
 
 
+def _unit_columns(what, **views):
+    """The BatchNorm entry points take a row stride only: a transposed or column-strided view would be read as if its columns were
+    adjacent (wrong statistics, no error from the library), so it is refused here."""
+    for name, t in views.items():
+        if t is not None and (t.dim() != 2 or t.stride(1) != 1):
+            raise ValueError(f"{what}: {name} must be a 2-D matrix with unit column stride (a column view of a wider matrix is fine), got "
+                             f"shape {tuple(t.shape)} strides {tuple(t.stride())}")
+
+
 def bn_train_stats(x, gamma, beta, eps, momentum, running_mean=None, running_var=None, num_batches_tracked=None):
     """Batch statistics of x [n, C] -> (mean, rstd, scale, shift), running statistics updated in place (tl_bn_train_stats)."""
     L = _hip.lib()
-    _hip.require_cuda(x, "x")
+    _unit_columns("bn_train_stats", x=x)
+    if not x.is_cuda:
+        raise RuntimeError(f"x must live on the GPU (got {x.device}); the HIP path has no CPU fallback")
     n, C = x.shape
     dev = x.device
     ws = torch.empty(int(L.tl_bn_ws_doubles(n, C)), dtype=torch.float64, device=dev)
@@ -309,6 +320,7 @@ def bn_train_bwd_from_parts(x, g, st, parts, nparts, dx_add=None, dx=None, dgb=N
     None if the views do not allow the vector kernel.  x, g, st, dx_add, dx (out) and dgb (out, [2, C]) may be column slices of wider
     tensors: a layer whose input gradient is computed in channel slices runs this once per slice."""
     L = _hip.lib()
+    _unit_columns("bn_train_bwd_from_parts", x=x, g=g, dx_add=dx_add, dx=dx)
     n, C = x.shape
     if dx is None:
         dx = torch.empty((n, C), dtype=x.dtype, device=x.device)
@@ -326,19 +338,34 @@ def bn_train_bwd_from_parts(x, g, st, parts, nparts, dx_add=None, dx=None, dgb=N
     return dx, dgb[0], dgb[1]
 
 
-def column_sum(x):
-    """sum over the rows of x [n, C] -> f32[C] on the BatchNorm statistics kernel (fp64 partial sums in a fixed order: deterministic;
-    one read of x at memory speed -- ATen's reduction over dim 0 of a [3.7 M, 32] matrix runs five times slower)."""
+def column_sum64(x):
+    """sum over the rows of x [n, C] -> f64[C] from the workspace of tl_bn_train_stats: its per-block fp64 partial sums (fixed row ranges,
+    lanes added in a fixed order), added up in fp64 -- deterministic, and a column whose sum cancels keeps the digits that the kernel's
+    fp32 mean, times n, would lose."""
+    L = _hip.lib()
+    _unit_columns("column_sum", x=x)
+    if not x.is_cuda:
+        raise RuntimeError(f"x must live on the GPU (got {x.device}); the HIP path has no CPU fallback")
     n, C = x.shape
-    ones = torch.ones(C, dtype=torch.float32, device=x.device)
-    st = bn_train_stats(x, ones, torch.zeros_like(ones), 1e-5, 0.0)
-    return st[0] * float(n)                                  # mean * n
+    ws = torch.empty(int(L.tl_bn_ws_doubles(n, C)), dtype=torch.float64, device=x.device)
+    st = torch.empty((4, C), dtype=torch.float32, device=x.device)
+    one = torch.ones(C, dtype=torch.float32, device=x.device)
+    _hip.check(L.tl_bn_train_stats(_hip.ptr(x), x.stride(0), n, C, _hip.dtype_code(x.dtype), _hip.ptr(one), _hip.ptr(one), 1e-5, 0.0, _hip.ptr(ws),
+                                   _hip.ptr(st[0]), _hip.ptr(st[1]), _hip.ptr(st[2]), _hip.ptr(st[3]), None, None, None, _hip.stream()), "tl_bn_train_stats")
+    return ws.view(-1, 2, C)[:, 0].sum(0)                    # ws = [blocks][sum, sum of squares][C]
+
+
+def column_sum(x):
+    """sum over the rows of x [n, C] -> f32[C]: column_sum64 rounded once (one read of x at memory speed -- ATen's reduction over dim 0 of a
+    [3.7 M, 32] matrix runs five times slower)."""
+    return column_sum64(x).float()
 
 
 def bn_train_bwd(x, dy, st, relu, dx_add=None):
     """(dx, dgamma, dbeta) of y = relu?(batchnorm_train(x)) given dy (tl_bn_train_bwd); st = bn_train_stats' result; dx_add (x's dtype
     and shape) is added to dx in the same pass."""
     L = _hip.lib()
+    _unit_columns("bn_train_bwd", x=x, dy=dy, dx_add=dx_add)
     n, C = x.shape
     dev = x.device
     ws = torch.empty(int(L.tl_bn_ws_doubles(n, C)), dtype=torch.float64, device=dev)
@@ -365,7 +392,9 @@ def gather_rows(x, idx):
 
 
 def scatter_add_rows(g, order, sorted_idx, n_rows):
-    """out[v] = sum of g[p] over idx[p] == v in ascending p (tl_scatter_add_rows); order / sorted_idx = stable argsort of idx / idx[order]."""
+    """out[v] = sum of g[p] over idx[p] == v in ascending p (tl_scatter_add_rows); order / sorted_idx = stable argsort of idx / idx[order],
+    idx NORMALISED to 0 <= idx < n_rows before the sort (the kernel groups equal sorted values: -1 and n_rows - 1 would be two groups
+    writing one row)."""
     L = _hip.lib()
     out = torch.empty((n_rows, g.shape[1]), dtype=g.dtype, device=g.device)
     _hip.check(L.tl_scatter_add_rows(_hip.ptr(g), g.stride(0), _hip.dtype_code(g.dtype), g.shape[1], _hip.ptr(order), _hip.ptr(sorted_idx), g.shape[0], n_rows,
