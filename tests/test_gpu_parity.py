@@ -948,7 +948,7 @@ def test_inverse_conv_one_hot_form(cin, cout, n_out):
                                                (32, 2, 1, 50000), (32, 3, 1, 70001), (64, 4, 1, 3000),     # the heads' output Linears (tl_linear_small.hip)
                                                (32, 32, 1, 100003), (64, 32, 1, 70000), (128, 64, 1, 40001), (192, 96, 1, 33000), (256, 128, 1, 31000),   # tl_wgrad_rows.hip
                                                (4, 32, 27, 50001), (128, 128, 27, 60500), (256, 128, 27, 60100), (32, 32, 27, 70001), (64, 32, 27, 65000), (64, 64, 27, 99999), (128, 64, 27, 61000),
-                                               (96, 96, 27, 50000), (192, 96, 27, 40000)])        # multiples of 96 below the dense form's row threshold: 96 x 96 pair-list blocks
+                                               (96, 96, 27, 50000), (192, 96, 27, 40000)])        # multiples of 96 below the dense form's row threshold: the shared-gout kernel with 64-wide (masked) blocks; 96 x 96 blocks need >= 100 000 rows
 def test_conv_wgrad_vs_dense_reference(cin, cout, K, n_out):
     """tl_conv_wgrad (present pairs only, fp32 MFMA, deterministic) vs gather + matmul in float64."""
     from treelearn_amd import ops

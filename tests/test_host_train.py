@@ -230,3 +230,81 @@ def test_batchnorm_entry_points_refuse_bad_views_before_any_launch():
     assert lib.tl_bn_train_bwd(p, 8, _hip.TL_BF16, p, 8, _hip.TL_F16, 16, 8, p, p, p, p, 1, p, p, p, p, 8, None, 0, None) == _hip.TL_ERR_ARG
     assert lib.tl_bn_train_bwd(p, 8, _hip.TL_F16, p, 8, _hip.TL_BF16, 16, 8, p, p, p, p, 1, p, p, p, p, 8, None, 0, None) == _hip.TL_ERR_ARG
 
+
+def test_weight_gradient_cases_have_an_exact_fp32_answer():
+    """tests/wgrad_cases.py, every generator at its smallest size: present pairs per tap stay under the cap, the float64 reference of Set A is a
+    multiple of 1/64, survives the round trip through fp32 and equals an integer recomputation; the special and one-pair tables hold what they
+    say; Set B's values are representable in their 16-bit type and one product of them is exact in fp32."""
+    import numpy as np
+    import wgrad_cases as C
+    for name, x, g, t, K in C.smallest_cases():
+        if t is not None:
+            assert t.dtype == np.int32 and t.shape == (K, g.shape[0]) and int((t >= 0).sum(1).max()) <= C.PAIR_CAP, name
+            assert t.min() >= -1 and t.max() < x.shape[0], name
+        ref = C.reference(x, g, t, K)
+        assert np.array_equal(ref * 64, np.rint(ref * 64)), name
+        assert np.array_equal(ref.astype(np.float32).astype(np.float64), ref), name
+        assert np.array_equal(ref * 64, C.reference_int64(x, g, t, K).astype(np.float64)), name
+        assert np.abs(ref).max() > 0, name
+    rng = np.random.default_rng(3)
+    t = C.special_table(rng, 27, 300, 350)
+    cnt = (t >= 0).sum(1)
+    assert cnt[0] == 0 and cnt[1] == 300 and np.array_equal(t[1], np.arange(300))
+    assert cnt[2] == 1 and t[2, 299] == 349 and cnt[3] == 1 and t[3, 0] == 0
+    assert cnt[4] == 300 and len(np.unique(t[4])) == 1
+    assert [int(c) for c in cnt[5:8]] == [15, 16, 17] and (t[5:8, 64:] == -1).all()
+    assert [int(c) for c in cnt[24:27]] == [1, 1, 1] and t[25, 299] == 0 and t[26, 0] == 349
+    assert 0 < cnt[8] < 300
+    assert (C.special_table(rng, 8, 1, 51) >= 0).sum(1).tolist() == [0, 1, 1, 1, 1, 1, 1, 1]           # one output row: what K and n_out allow
+    for n_out, tiles in ((1, (64,)), (20, (16, 64)), (5000, (64, 128, 256, 4096))):
+        t = C.one_pair_table(rng, 27, n_out, n_out + 50, tiles)
+        assert ((t >= 0).sum(1) == 1).all()
+        rows = [int(np.flatnonzero(t[k] >= 0)[0]) for k in range(27)]
+        assert rows[0] == 0 and rows[1] == n_out - 1 and t[0, 0] == 0 and t[1, n_out - 1] == n_out + 49
+        if n_out >= 27:
+            assert len(set(rows)) == 27
+    assert {63, 64, 127, 128, 255, 256, 4095, 4096} <= set(rows)
+    for dt, bits in (("bf16", 8), ("f16", 11)):
+        v = C.mantissa(rng, (64, 8), dt)
+        assert np.array_equal(C.round_to(v, dt), v) and np.abs(v).min() >= 2.0 ** -4 and np.abs(v).max() <= 2.0 ** 4
+        m, _ = np.frexp(v.astype(np.float64))
+        assert np.array_equal(m * 2 ** bits, np.rint(m * 2 ** bits))                                    # `bits` significant bits
+        p = v[:32].astype(np.float64) * v[32:].astype(np.float64)
+        assert np.array_equal(p.astype(np.float32).astype(np.float64), p)
+    assert np.array_equal(C.round_to(np.array([1.00390625, 1.01171875], np.float32), "bf16"), np.array([1.0, 1.015625], np.float32))   # ties to even, both ways
+    a = np.concatenate([rng.normal(size=4096) * 10.0 ** rng.integers(-30, 30, size=4096), [-3.0e38, 1e-40, 0.0]]).astype(np.float32)
+    assert np.array_equal(C.round_to(a, "bf16"), torch.from_numpy(a).bfloat16().float().numpy())
+    # the case lists hold every value the kernels' constants ask for
+    tiles = lambda c: 1 if c <= 32 else (3 if 64 < c <= 96 else 2)                                       # noqa: E731
+    seen = {}
+    for ci, co, K, n, _ in C.GENERIC:
+        seen.setdefault((tiles(co), tiles(ci)), set()).add(n)
+    assert len(seen) == 9 and all(len(v) >= 2 for v in seen.values())
+    assert {c[3] for c in C.GENERIC} == {1, 2, 63, 64, 65, 4095, 4096, 4097, 16384, 16385} and {c[2] for c in C.GENERIC} == {1, 8, 27}
+    assert C.dense_rows(64, 64) == [1, 63, 64, 65, 511, 513, 88 * 64 + 1, 136 * 64 + 1] and C.dense_rows(96, 96)[-1] == 48 * 128 + 1
+
+
+def test_weight_gradient_tuning_keys_reach_the_f16_compilation():
+    """The weight-gradient units are compiled twice (bf16 and IEEE half).  tl_set_tuning and tl_conv_wgrad_ws_floats belong to the first compilation;
+    the half launchers must see the same keys, or a workspace sized under wgrad_dense = 0 / wgrad_rows = 0 / wgrad_dma = 2 / wgrad_dense_min_rows is
+    too small for what the half kernels write (96 -> 96, 100 001 rows, wgrad_dense = 0: 28 partial sets allocated, 40 written)."""
+    import wgrad_cases as C
+    from treelearn_amd import _hip
+    L = _hip.lib()
+    f16 = L.tl_conv_wgrad_ws_floats_f16
+    f16.restype, f16.argtypes = ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+    shapes = [(100001, 27, 96, 96), (100000, 27, 192, 96), (70000, 27, 64, 64), (61000, 27, 128, 64), (30000, 1, 32, 32), (50001, 27, 4, 32), (500, 27, 64, 64)]
+    sizes = set()
+    try:
+        for keys in ({}, dict(wgrad_dense=0), dict(wgrad_rows=0), dict(wgrad_dma=0), dict(wgrad_dma=2), dict(wgrad_dense_min_rows=1)):
+            for k, v in {**C.KNOB_DEFAULTS, **keys}.items():
+                assert L.tl_set_tuning(k.encode(), v) == 0
+            got = tuple(int(L.tl_conv_wgrad_ws_floats(*s)) for s in shapes)
+            assert got == tuple(int(f16(*s)) for s in shapes), keys
+            sizes.add(got)
+    finally:
+        for k, v in C.KNOB_DEFAULTS.items():
+            L.tl_set_tuning(k.encode(), v)
+    assert len(sizes) == 5                                          # every key moves some size (wgrad_dma = 0 keeps the slot counts)
+    per = 27 * 96 * 96
+    assert L.tl_conv_wgrad_ws_floats(100001, 27, 96, 96) == 40 * per and f16(100001, 27, 96, 96) == 40 * per

@@ -12,10 +12,9 @@
 #define tl_conv_wgrad_ref tl_conv_wgrad_ref_f16
 #define tl_conv_wgrad_blk tl_conv_wgrad_blk_f16
 #define tl_conv_wgrad_blk_ws_floats tl_conv_wgrad_blk_ws_floats_f16
-#define g_wgrad_dma g_wgrad_dma_f16
-#define g_wgrad_dense g_wgrad_dense_f16
-#define g_wgrad_dense_min_rows g_wgrad_dense_min_rows_f16
-#define g_wgrad_rows g_wgrad_rows_f16
+// (the tuning keys g_wgrad_dma, g_wgrad_dense, g_wgrad_dense_min_rows and g_wgrad_rows keep their names: ONE copy, defined by the default compilation
+// and read by both -- tl_set_tuning and tl_conv_wgrad_ws_floats see what the f16 launchers see.  With a copy of their own the f16 launchers ignored the
+// keys while the workspace was sized by them: wgrad_dense = 0 or wgrad_rows = 0 made an f16 call write past tl_conv_wgrad_ws_floats)
 #define tl_launch_wgrad_reduce tl_launch_wgrad_reduce_f16
 #define tl_wgrad_dense_slots tl_wgrad_dense_slots_f16
 #define tl_launch_wgrad_dense tl_launch_wgrad_dense_f16

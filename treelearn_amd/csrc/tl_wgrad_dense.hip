@@ -684,7 +684,14 @@ __global__ void __launch_bounds__(kWB_NT) k_wgrad_blk(const uint16_t* __restrict
 
 }  // namespace
 
+#ifdef TL_F16_BUILD                // the keys live in the default compilation (tl_f16_train.h)
+extern int g_wgrad_dma, g_wgrad_dense;
+extern int64_t g_wgrad_dense_min_rows;
+#else
 int g_wgrad_dma = 1;              // tl_set_tuning("wgrad_dma", 0): the register-staged form everywhere
+int g_wgrad_dense = 1;            // tl_set_tuning("wgrad_dense", 0) restores the pair-list kernels of tl_wgrad.hip everywhere
+int64_t g_wgrad_dense_min_rows = 60000;
+#endif
 
 // shared with tl_wgrad.hip: gw = ordered sum of `nparts` partial tile sets of `per` floats (per % 4 == 0, 16-B aligned)
 int tl_launch_wgrad_reduce(const float* ws, int64_t nparts, int64_t per, float* gw, hipStream_t s, int K, int Cout, int Cin, int ref_layout) {
@@ -692,9 +699,6 @@ int tl_launch_wgrad_reduce(const float* ws, int64_t nparts, int64_t per, float* 
   k_wgrad_reduce_par<<<(unsigned)tl_cdiv(per / 4, 16), 256, 0, s>>>(ws, (int)nparts, per, gw, remap ? K : 0, Cout, Cin);
   return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
 }
-
-int g_wgrad_dense = 1;            // tl_set_tuning("wgrad_dense", 0) restores the pair-list kernels of tl_wgrad.hip everywhere
-int64_t g_wgrad_dense_min_rows = 60000;
 
 // row slots (= partial tile sets) of the dense form for a shape, 0 if the shape is not served
 

@@ -275,7 +275,11 @@ int launch(const uint16_t* x, int64_t x_ld, const uint16_t* g, int64_t g_ld, int
 
 }  // namespace
 
+#ifdef TL_F16_BUILD
+extern int g_wgrad_rows;          // the key lives in the default compilation (tl_f16_train.h)
+#else
 int g_wgrad_rows = 1;             // tl_set_tuning("wgrad_rows", 0): the pair-list kernels for K = 1 as well
+#endif
 
 // partial tile sets (workgroups along x) of the row-streaming form for a K = 1 shape, 0 if the shape is not served
 int tl_wgrad_rows_parts(int64_t n, int Cin, int Cout) {
