@@ -691,6 +691,48 @@ int tl_tree_ground(const double* sorted_xyz, int64_t n, const int64_t* start, in
                    double slice_height, double slice_thickness, double dbh_max_radius, int64_t dbh_min_points, double* ground_table,
                    int64_t* ground_n, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ stem profiles of a labelled cloud (csrc/tl_stem.hip)
+ * A circle per horizontal slab along every stem, tracked bottom-up, and from the accepted circles the stem volume, the diameter at breast
+ * height, the lean and the taper.  The semantics are the project's own and have no reference call site: tests/stem_restatement.py
+ * restates them in numpy float64.  All arithmetic is f64 in plain operators, no fma contraction; distances are compared squared.
+ * The rows are those of tl_inventory_gather (label order, sorted_label i64[n] = the label of each, tree t = label t + 1);
+ * tree f64[n_trees, 4] = px, py, z_ref, z_top per tree: the inventory's position and z_top, and z_low or z_ground as the reference.
+ * Slab k of a tree exists when k < max_slices and h_k = first_height + k * step <= z_top - z_ref (none for a NaN); zc_k = z_ref + h_k,
+ * lo_k = zc_k - thickness / 2, hi_k = zc_k + thickness / 2.  S, the profile width, is the largest slab count of any tree (the caller's).
+ * tl_stem_keys: keys i64[n]: tree * S + k for a row with (x - px)^2 + (y - py)^2 < corridor^2 that lies in slab k, lo_k <= z < hi_k (the
+ *   lowest such k; found among floor(q) - 1 .. floor(q) + 1, q = ((z - z_ref) - (first_height - thickness / 2)) / step, by the exact
+ *   rule), else the sentinel n_trees * S: also for a label outside 1 .. n_trees, a non-finite value or a q outside (-2, max_slices + 1).
+ *   The caller sorts the keys (stable), gathers the rows below the sentinel in key order (stem_xyz, n rows) and takes
+ *   slab_start i64[n_trees * S + 1] = the first row of every key.
+ * tl_stem_profile: one workgroup per tree walks k = 0 .. with c = (px, py), R = start_radius, r_prev = NaN, misses = 0.  A slab after the
+ *   walk stopped: state 0, n = 0.  Otherwise n = the slab's rows with u*u + v*v < R*R, u = x - c.x, v = y - c.y; with n >= min_points the
+ *   circle fit of tl_tree_inventory on (u, v) (the same device functions), rmse = sqrt(sum((sqrt(du*du + dv*dv) - r)^2) / n).  Accepted
+ *   (state 1) when the fit succeeded, rmse <= max_rmse, min_radius <= r <= max_radius and r <= max_growth * r_prev (or r_prev is NaN):
+ *   x = cx + c.x, y = cy + c.y, then c = (x, y), r_prev = r, R = search_factor * r + search_margin, misses = 0.  Otherwise state 2,
+ *   misses += 1, and the walk stops at misses >= max_misses.
+ *   profile f64[n_trees, S, 5] = h, x, y, r, rmse (NaN in the last four unless accepted; h = NaN for a slab the tree does not have);
+ *   pcount i64[n_trees, S, 2] = n, state; slices i64[n_trees] = accepted slabs m; summary f64[n_trees, 6], over them in ascending k:
+ *   stem_base_h, stem_top_h = h of the first / last; stem_volume = (PI * (r0 * r0)) * h_first, then for every consecutive accepted pair
+ *   V = V + ((PI / 3.0) * (h_j - h_i)) * ((r_i * r_i + r_i * r_j) + r_j * r_j); dbh_stem = 2.0 * (r_i + (r_j - r_i) * ((dbh_height - h_i)
+ *   / (h_j - h_i))) for the first such pair with h_i <= dbh_height <= h_j, else NaN; stem_lean = atan2(sqrt(dx*dx + dy*dy), h_last -
+ *   h_first) * (180.0 / PI), (dx, dy) = last centre - first centre; stem_taper = sum((h - hm)(d - dm)) / sum((h - hm)^2), d = 2.0 * r,
+ *   hm = sum(h) / m, dm = sum(d) / m.  All six NaN for m = 0, lean and taper NaN for m < 2.
+ *   Sums: registers, a fixed wave butterfly, then the wave sums in wave order -- no float atomics, the same bits run to run.
+ * A null or misaligned pointer, a negative size, S > max_slices or a parameter outside its constraint (first_height, step, corridor,
+ * start_radius, max_rmse, dbh_height > 0; 0 < thickness <= step; max_slices in 1 .. 256; search_factor, max_growth >= 1; search_margin
+ * >= 0; min_points >= 3; 0 < min_radius <= max_radius; max_misses >= 1; all finite): TL_ERR_ARG, nothing launched.  n_trees = 0 or S = 0,
+ * and tl_stem_keys with n = 0: TL_OK without a launch (outputs untouched).  tl_stem_profile with n = 0 rows
+ * still walks every tree: each visited slab is a miss. */
+typedef struct tl_stem_params {
+  double first_height, step, thickness, corridor, start_radius, search_factor, search_margin, max_rmse, min_radius, max_radius, max_growth,
+      dbh_height;
+  int64_t max_slices, min_points, max_misses;
+} tl_stem_params;
+int tl_stem_keys(const double* sorted_xyz, const int64_t* sorted_label, int64_t n, const double* tree, int64_t n_trees, int64_t S,
+                 const tl_stem_params* params, int64_t* keys, tl_stream_t stream);
+int tl_stem_profile(const double* stem_xyz, int64_t n, const int64_t* slab_start, const double* tree, int64_t n_trees, int64_t S,
+                    const tl_stem_params* params, double* profile, int64_t* pcount, double* summary, int64_t* slices, tl_stream_t stream);
+
 /* ------------------------------------------------------------------ LAS point records (csrc/tl_las.hip)
  * The record passes of the LAS reader and writer (treelearn_amd/util/las.py parses and writes the headers on the host).  The layout is
  * the ASPRS one and the rules are restated in numpy in tests/las_restatement.py; all arithmetic is f64 in plain operators, no fma

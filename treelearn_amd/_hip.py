@@ -95,6 +95,12 @@ class ForwardArgs(_c.Structure):           # tl_forward_args
                 ("level_n", _i64 * TL_MAX_LEVELS), ("blocked_used", _i32), ("launches", _i32)]
 
 
+class StemParams(_c.Structure):            # tl_stem_params
+    _fields_ = [(k, _c.c_double) for k in ("first_height", "step", "thickness", "corridor", "start_radius", "search_factor", "search_margin",
+                                           "max_rmse", "min_radius", "max_radius", "max_growth", "dbh_height")] + \
+               [(k, _i64) for k in ("max_slices", "min_points", "max_misses")]
+
+
 _I4 = _i32 * 4
 _I3 = _i32 * 3
 
@@ -184,6 +190,8 @@ PROTOTYPES = {
     "tl_dtm_fill": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "tl_dtm_sample": (_i32, [_vp, _i32, _i64, _i64, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "tl_tree_ground": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _c.c_double, _c.c_double, _c.c_double, _i64, _vp, _vp, _vp]),
+    "tl_stem_keys": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _c.POINTER(StemParams), _vp, _vp]),
+    "tl_stem_profile": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _c.POINTER(StemParams), _vp, _vp, _vp, _vp, _vp]),
     "tl_las_decode": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _c.c_double * 3, _c.c_double * 3, _vp, _i32, _i64, _i32, _vp]),
     "tl_las_encode": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _i64, _c.c_double * 3, _c.c_double * 3, _vp, _i64, _vp, _vp, _vp, _vp]),
     "tl_pointwise_eval_ws_bytes": (_i64, [_i64]),

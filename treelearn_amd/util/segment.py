@@ -158,14 +158,20 @@ def segment_from_pointwise(coords, offset_predictions, instance_preds, shape_cfg
 
 
 def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=None, return_type="original", logger=None,
-                   return_pointwise=False, inventory=False, inventory_cfg=None, terrain=False, terrain_cfg=None):
+                   return_pointwise=False, inventory=False, inventory_cfg=None, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None):
     """points: N x 3 or N x 4 (x y z [label]) f64, host or device.  Returns numpy arrays: coords (f64, input frame), labels (i64),
     categories (per tree 1..T, index into CATEGORIES), and with return_pointwise the arrays of pipeline.py:100-111 (ensembled rows).
     inventory=True adds result["inventory"]: util.inventory.tree_inventory of the returned coords / labels, computed on the device in
     the centred frame and un-centred like the coords; inventory_cfg holds any of its five parameters.
     terrain=True adds result["terrain"] (util.terrain: the DTM of the label-0 rows of the returned cloud, computed on the device in the
     centred frame; the un-centred Terrain.to_host()) and result["height_above_ground"] (f64 [N], row-aligned with coords); terrain_cfg
-    holds any of its five parameters.  With inventory=True as well, the inventory gets the ground columns."""
+    holds any of its five parameters.  With inventory=True as well, the inventory gets the ground columns.
+    stem=True implies inventory=True and adds util.stem's columns and result["inventory"]["stem_profile"] (the circle of every slab along
+    every stem); stem_cfg holds any of util.stem's parameters."""
+    if stem:
+        from .stem import check_params as check_stem
+        stem_cfg = check_stem(stem_cfg)                                               # before any GPU work
+        inventory = True
     if inventory:
         from .inventory import check_params, tree_inventory
         inventory_cfg = check_params(inventory_cfg)                                   # before any GPU work
@@ -219,7 +225,8 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
         result["height_above_ground"] = host(dtm.height_above_ground(r["coords"]))
     if inventory:
         _log(logger, "computing the tree inventory")
-        result["inventory"] = tree_inventory(r["coords"], r["labels"], offset=mean, terrain=dtm, **inventory_cfg)
+        result["inventory"] = tree_inventory(r["coords"], r["labels"], offset=mean, terrain=dtm, stem=stem, stem_cfg=stem_cfg if stem else None,
+                                             **inventory_cfg)
     if return_pointwise:
         pw = dict(coords=coords, offset_predictions=off, offset_labels=offl, semantic_prediction_logits=sem, semantic_labels=seml,
                   instance_labels=instl, backbone_feats=bb, input_feats=infeat, instance_preds=inst, instance_preds_after_initial_clustering=initial)
@@ -278,7 +285,8 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
     and individual_trees/non_trees.<fmt> (first format; coordinates shifted by the mean of the returned cloud, as save_treewise does);
     pointwise_results/pointwise_results.npz + cluster_coords_initial / cluster_coords (first format) when the result holds them;
     tree_inventory.csv (util.inventory.write_inventory, with the category names) when the result holds an inventory; terrain.npz
-    (util.terrain.write_terrain) and height_above_ground.npy when it holds a terrain."""
+    (util.terrain.write_terrain) and height_above_ground.npy when it holds a terrain; stem_profiles.npz (util.stem.write_stem_profiles) when
+    the inventory holds stem profiles."""
     save_formats = list(save_formats)
     check_formats(save_formats)
     coords, labels = np.asarray(result["coords"], np.float64), np.asarray(result["labels"], np.int64)
@@ -322,6 +330,9 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
         from .inventory import write_inventory
         os.makedirs(out_dir, exist_ok=True)
         write_inventory(os.path.join(out_dir, "tree_inventory.csv"), result["inventory"], categories=result["categories"])
+        if "stem_profile" in result["inventory"]:
+            from .stem import write_stem_profiles
+            write_stem_profiles(os.path.join(out_dir, "stem_profiles.npz"), result["inventory"])
     if "terrain" in result:
         from .terrain import write_terrain
         os.makedirs(out_dir, exist_ok=True)
@@ -390,10 +401,14 @@ def parse_args(argv=None):
     ap.add_argument("--terrain", action="store_true", help="write terrain.npz and height_above_ground.npy; with --inventory, add the ground columns")
     from . import terrain as _terrain
     _terrain.add_arguments(ap)
+    ap.add_argument("--stem", action="store_true", help="write stem_profiles.npz and add the stem columns to tree_inventory.csv (implies --inventory)")
+    from . import stem as _stem
+    _stem.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         check_params(params_of(a))
         _terrain.check_params(_terrain.params_of(a))
+        _stem.check_params(_stem.params_of(a))
     except ValueError as e:
         ap.error(str(e))
     check_formats(a.formats)
@@ -434,11 +449,12 @@ def main(argv=None):
                     tau_vert=a.tau_vert, tau_off=a.tau_off)
     shape = dict(SHAPE_CFG, alpha=a.alpha, buffer_size_to_determine_edge_trees=a.edge_buffer, outer_remove=a.outer_remove)
     with torch.no_grad():
-        from . import terrain as _terrain
+        from . import stem as _stem, terrain as _terrain
         from .inventory import params_of
         res = segment_forest(points, model, sample, grouping, shape, a.return_type, logger, return_pointwise=a.save_pointwise,
-                             inventory=a.inventory, inventory_cfg=params_of(a) if a.inventory else None,
-                             terrain=a.terrain, terrain_cfg=_terrain.params_of(a) if a.terrain else None)
+                             inventory=a.inventory, inventory_cfg=params_of(a) if a.inventory or a.stem else None,
+                             terrain=a.terrain, terrain_cfg=_terrain.params_of(a) if a.terrain else None,
+                             stem=a.stem, stem_cfg=_stem.params_of(a) if a.stem else None)
     plot_name = os.path.splitext(os.path.basename(a.forest))[0]
     save_results(res, a.out, plot_name, a.formats, save_treewise=not a.no_treewise, save_pointwise=a.save_pointwise)
     cats = np.bincount(res["categories"], minlength=3)
