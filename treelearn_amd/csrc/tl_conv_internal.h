@@ -311,6 +311,138 @@ static __device__ __forceinline__ void epi_finish_wg(const ConvP& p, float* Es, 
   }
 }
 
+// ---- the stream / stream-q kernels' inference epilogue (epi_mode == TL_EPI_NONE).  Rule: after a wave's first store it issues no vector-memory
+// load and no vmcnt wait -- vmcnt counts stores too, in order, so a wait for a load behind a store drains that store.  The views' affines
+// come from a workgroup copy in LDS (ds_read_b128 is counted by lgkmcnt), the residual rows are requested before the accumulators are
+// parked.  Exception: a kernel with more 32 x 32 blocks per wave than it can hold residual rows for (PD < RB * NB below) requests block
+// b + PD when block b has been stored, and the wait for those rows drains the stores of block b.  The training modes and the other kernel
+// families keep the per-view loads of epi_views8 / epi_views8_red above, whose text and code are unchanged.
+//
+// 8 residual elements as loaded (request and use are separate so that the request can go out ahead of the stores)
+template <bool BF16> struct EpiRes { u32x4 r[BF16 ? 1 : 2]; };
+template <bool BF16>
+static __device__ __forceinline__ EpiRes<BF16> res_load8(const void* res, int64_t elem) {
+  EpiRes<BF16> r;
+  if constexpr (BF16) r.r[0] = *reinterpret_cast<const u32x4*>((const uint16_t*)res + elem);
+  else { r.r[0] = *reinterpret_cast<const u32x4*>((const float*)res + elem); r.r[1] = *reinterpret_cast<const u32x4*>((const float*)res + elem + 4); }
+  return r;
+}
+template <bool BF16>
+static __device__ __forceinline__ EpiRes<BF16> res_none8() {
+  EpiRes<BF16> r;
+#pragma unroll
+  for (int i = 0; i < (BF16 ? 1 : 2); ++i) r.r[i] = u32x4{0u, 0u, 0u, 0u};
+  return r;
+}
+template <bool BF16>
+static __device__ __forceinline__ void res_apply8(const EpiRes<BF16>& r, float (&v)[8]) {   // v += the loaded elements: the sums of res_add8
+  if constexpr (BF16) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { v[2 * q] += bf16_lo(r.r[0][q]); v[2 * q + 1] += bf16_hi(r.r[0][q]); }
+  } else {
+    const f32x4 r0 = __builtin_bit_cast(f32x4, r.r[0]), r1 = __builtin_bit_cast(f32x4, r.r[1]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { v[q] += r0[q]; v[q + 4] += r1[q]; }
+  }
+}
+// workgroup: copy the views' affines to LDS, aff[view][scale, shift][cout] (6 * cout floats, cout <= the workgroup's threads), in two steps so
+// that the kernel can request them first thing and park them once something older has had to be waited for anyway (no stall of their own,
+// no register held across the tap loop); the caller's next __syncthreads() publishes them
+struct EpiAffRegs { float a[6]; };
+static __device__ __forceinline__ EpiAffRegs epi_aff_fetch(const ConvP& p, int tid, int cout) {
+  const float* src[6] = {p.out_scale, p.out_shift, p.out2 ? p.out2_scale : nullptr, p.out2 ? p.out2_shift : nullptr,
+                         p.out3 ? p.out3_scale : nullptr, p.out3 ? p.out3_shift : nullptr};
+  EpiAffRegs r;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) r.a[a] = (src[a & ~1] && tid < cout) ? src[a][tid] : 0.f;
+  return r;
+}
+static __device__ __forceinline__ void epi_aff_put(const EpiAffRegs& r, float* aff, int tid, int cout) {
+  if (tid < cout) {
+#pragma unroll
+    for (int a = 0; a < 6; ++a) aff[a * cout + tid] = r.a[a];
+  }
+}
+// the stores of all views of one row vector with the affines read from the LDS copy, each right in front of its store (the scheduling
+// barriers keep hipcc from hoisting all three: 48 registers); epi_store8 with LDS pointers is the arithmetic of every other kernel
+template <bool BF16>
+static __device__ __forceinline__ void epi_stores8_lds(const ConvP& p, const float* aff, int cout, int64_t row, int c0, const float (&v)[8]) {
+  if (p.out_scale) epi_store8<BF16>(p.out, p.out_ld, aff, aff + cout, p.out_relu, row, c0, v);
+  else epi_store8<BF16>(p.out, p.out_ld, nullptr, nullptr, p.out_relu, row, c0, v);
+  if (p.out2) {
+    __builtin_amdgcn_sched_barrier(0);
+    if (p.out2_scale) epi_store8<BF16>(p.out2, p.out2_ld, aff + 2 * cout, aff + 3 * cout, p.out2_relu, row, c0, v);
+    else epi_store8<BF16>(p.out2, p.out2_ld, nullptr, nullptr, p.out2_relu, row, c0, v);
+  }
+  if (p.out3) {
+    __builtin_amdgcn_sched_barrier(0);
+    if (p.out3_scale) epi_store8<BF16>(p.out3, p.out3_ld, aff + 4 * cout, aff + 5 * cout, p.out3_relu, row, c0, v);
+    else epi_store8<BF16>(p.out3, p.out3_ld, nullptr, nullptr, p.out3_relu, row, c0, v);
+  }
+}
+// a block's residual requests: the lane's two row vectors (rows (lane >> 2) and 16 + (lane >> 2), channels col0 + 8 (lane & 3) ..).  Rows past the
+// end re-read the last row (never used): unconditional loads, no exec-masked branch for the wait counters to lose track at
+template <bool BF16>
+static __device__ __forceinline__ void epi_block32_res(const ConvP& p, int lane, int64_t row0, int col0, EpiRes<BF16> (&rs)[2]) {
+#pragma unroll
+  for (int e0 = 0; e0 < 2; ++e0) {
+    int64_t orow = row0 + (lane >> 2) + 16 * e0;
+    orow = orow < p.n_out ? orow : p.n_out - 1;
+    rs[e0] = p.res ? res_load8<BF16>(p.res, orow * p.res_ld + col0 + (lane & 3) * 8) : res_none8<BF16>();
+  }
+}
+// s_waitcnt operand (gfx9 layout: vmcnt [3:0] + [15:14], expcnt [6:4], lgkmcnt [11:8]): vmcnt(0), the other two counters at their maxima = not waited for
+constexpr int TL_WAITCNT_VM0 = 0x0F70;
+// The epilogue itself (call it straight after the tap loop, all waves, epi_mode == TL_EPI_NONE): the wave's RB x NB accumulator blocks, one at
+// a time through its LDS tile ew = Es + wave * 32 * EP (Es may alias the weight ring: the barrier in here retires it), to the views.
+// PD = blocks whose residual rows are requested before that barrier (epi_pd: all of them in the 16-bit kernels of up to four blocks).
+// aff = the LDS copy made by epi_aff_put (outside Es).
+// QMAP: MFMA row m is tile row ((m >> 2) & 7) + 8 (m & 3) (the quad-gather kernel's row order) instead of m.
+template <bool BF16> constexpr int epi_pd(int nblk) { return nblk < (BF16 ? 4 : 2) ? nblk : (BF16 ? 4 : 2); }
+template <bool BF16, int W, int EP, int NB, int RB, bool QMAP, int PD>
+static __device__ __forceinline__ void epi_wave_tail_lds(const ConvP& p, float* Es, const float* aff, int tid, int64_t r0, const f32x16 (&acc)[RB][NB]) {
+  constexpr int NBLK = RB * NB;
+  static_assert(PD >= 1 && PD <= NBLK, "residual blocks requested ahead");
+  const int lane = tid & 63, wv = tid >> 6, fi = lane & 31, fh = lane >> 5;
+  EpiRes<BF16> rs[PD][2];
+#pragma unroll
+  for (int b = 0; b < PD; ++b) epi_block32_res<BF16>(p, lane, r0 + (b / NB) * 32, (b % NB) * 32, rs[b]);
+  __syncthreads();
+  // one wait for the residual rows, here, outside the per-row branches: left to the compiler, it waits at each use inside the
+  // `if (row < n_out)` branches again (the counters' state is merged pessimistically where branches join) -- with vmcnt(0), behind stores.
+  // Unconditional on purpose: under `if (p.res)` it is one more branch the requests' own `p.res` branches are not linked with, and the
+  // waits behind the stores come back; without a residual nothing is outstanding and the wait costs nothing.
+  __builtin_amdgcn_s_waitcnt(TL_WAITCNT_VM0);
+  asm volatile("; tl_epi_lds_tail");                 // (a comment in the assembly: tools/check_conv_epilogue.py finds the tail by it)
+  float* ew = Es + wv * 32 * EP;
+#pragma unroll
+  for (int b = 0; b < NBLK; ++b) {
+    const int rb = b / NB, nb = b % NB;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int trow = QMAP ? 2 * (r >> 2) + fh + 8 * (r & 3) : (r & 3) + 8 * (r >> 2) + 4 * fh;
+      ew[trow * EP + fi] = acc[rb][nb][r];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int e0 = 0; e0 < 2; ++e0) {
+      const int e = lane + e0 * 64;                        // 32 rows x 4 vectors of 8 channels
+      const int rr = e >> 2, cvv = e & 3;
+      const int64_t orow = r0 + rb * 32 + rr;
+      if (orow < p.n_out) {
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(ew + rr * EP + cvv * 8), v1 = *reinterpret_cast<const f32x4*>(ew + rr * EP + cvv * 8 + 4);
+        float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+        if (p.res) res_apply8<BF16>(rs[b % PD][e0], v);
+        epi_stores8_lds<BF16>(p, aff, NB * 32, orow, nb * 32 + cvv * 8, v);
+      }
+    }
+    if (b + PD < NBLK) epi_block32_res<BF16>(p, lane, r0 + ((b + PD) / NB) * 32, ((b + PD) % NB) * 32, rs[b % PD]);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
 // One lane's 27 rulebook entries from the column form (9 bases + presence mask, tl_rulebook_compact)
 static __device__ __forceinline__ void decode_ctab(const int32_t* __restrict__ ctab, int64_t n, int64_t row, bool rvalid, int (&idx)[27]) {
   int base[9];

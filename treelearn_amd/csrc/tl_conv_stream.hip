@@ -20,6 +20,24 @@ namespace {
 constexpr int WAVES = 8;
 constexpr int NT = WAVES * 64;
 
+// Which epilogue an instantiation's inference launches take (tl_conv_internal.h): the number of 32 x 32 blocks whose residual rows are requested
+// ahead of the first store (epi_wave_tail_lds, affines from an LDS copy), or 0 = the per-view loads of epi_block32 only.  Named by shape:
+//   three column blocks in one row block: one block ahead -- more costs instantiations a wave per SIMD;
+//   kernels that sit at an occupancy step or already spill, where holding both forms costs a wave per SIMD or more scratch, stay on the
+//   per-view loads: exact fp32 64 -> 64 and 192 -> 96 (27 taps) and 96 -> 64 (8 taps); bf16x3 128 -> 128 (27 taps) and 64 -> 96 (8 taps);
+//   the 16-bit one-hot inverse conv 128 -> 96.
+template <bool BF16, int K, int NB, int UN, int RB, bool OH, bool X3>
+constexpr int stream_epi_ahead() {
+  constexpr bool exact_f32 = !BF16 && !X3;
+  constexpr bool f32_64_64 = exact_f32 && K == 27 && NB == 2 && UN == 2, f32_192_96 = exact_f32 && K == 27 && NB == 3 && UN == 6;
+  constexpr bool f32_96_64_k8 = exact_f32 && K == 8 && NB == 2 && UN == 3;
+  constexpr bool x3_128_128 = X3 && K == 27 && NB == 4 && UN == 4, x3_64_96_k8 = X3 && K == 8 && NB == 3 && UN == 2;
+  constexpr bool oh_128_96 = BF16 && OH && K == 8 && NB == 3 && UN == 4;
+  if (f32_64_64 || f32_192_96 || f32_96_64_k8 || x3_128_128 || x3_64_96_k8 || oh_128_96) return 0;
+  if (NB == 3 && RB == 1) return 1;
+  return epi_pd<BF16>(RB * NB);
+}
+
 // OH (inverse conv, one valid table entry per output row): the row's single input row is gathered ONCE and routed to its
 // tap by a per-lane select, instead of K gathers of which K - 1 are out of range.
 // X3 (fp32 storage only): the contraction runs as split-bf16 products (tl_conv_internal.h: mma16_x3) on weights in the tl_pack_weight_x3 form
@@ -38,12 +56,18 @@ __global__ void __launch_bounds__(NT, OCC) k_conv_stream(ConvP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Bs = smem;                                                          // [2][COUT][BROW]
   float* Es = reinterpret_cast<float*>(smem);                               // epilogue alias of Bs: [WAVES][32][EP]
+  constexpr int PD = stream_epi_ahead<BF16, K, NB, UN, RB, OH, X3>();
+  constexpr int TAPB = 2 * COUT * BROW, EPB = WAVES * 32 * EP * 4;
+  [[maybe_unused]] float* Af = reinterpret_cast<float*>(smem + (TAPB > EPB ? TAPB : EPB));   // PD > 0: [3][2][COUT] the views' affines (epi_aff_put), live to the end
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int fi = lane & 31, fh = lane >> 5;
   const int tile = xcd_tile(blockIdx.x, p.nblk);
   const int64_t r0 = (int64_t)tile * (WAVES * WROWS) + wv * WROWS;
 
+  static_assert(COUT <= NT, "one affine element per thread");
+  [[maybe_unused]] EpiAffRegs afr = {};
+  if constexpr (PD > 0) afr = epi_aff_fetch(p, tid, COUT);    // requested ahead of the rulebook: parking them below waits for nothing younger
   int idx[K][RB];
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) {
@@ -107,6 +131,7 @@ __global__ void __launch_bounds__(NT, OCC) k_conv_stream(ConvP p) {
     }
   };
 
+  if constexpr (PD > 0) epi_aff_put(afr, Af, tid, COUT);
   // prologue: weights of tap 0 -> LDS; taps 1..WA-1 of the weights and 0..DA-1 of A in flight, interleaved in tap order
   load_b(0, bw0);
   [[maybe_unused]] u32x4 a1[RB][UN][NJ];                   // OH: the one gathered row per output row
@@ -197,6 +222,12 @@ __global__ void __launch_bounds__(NT, OCC) k_conv_stream(ConvP p) {
   }
 
   // epilogue, one 32x32 block at a time through a wave-private LDS transposition buffer (aliases the weight tiles)
+  if constexpr (PD > 0) {
+    if (p.epi_mode == TL_EPI_NONE) {                 // inference: affines from LDS, residual ahead, stores back to back (workgroup-uniform)
+      epi_wave_tail_lds<BF16, WAVES, EP, NB, RB, false, PD>(p, Es, Af, tid, r0, acc);
+      return;
+    }
+  }
   __syncthreads();
   float* ew = Es + wv * 32 * EP;
   float red0[NB], red1[NB];
@@ -226,7 +257,7 @@ int launch(ConvP p, hipStream_t s) {
   constexpr int OCC = (OH && X3) ? 2 : ((VG <= 120 || (X3 && NB * UN <= 4)) ? 4 : 2);      // (the split-bf16 form is latency-bound at two waves per SIMD: measured;
                                                                                              //  its one-hot form also holds the split row: 48 registers more)
   const size_t wt = 2 * (size_t)NB * 32 * (UN * 32 * EB + 16), ep = (size_t)WAVES * 32 * 36 * 4;
-  const size_t lds = wt > ep ? wt : ep;
+  const size_t lds = (wt > ep ? wt : ep) + (stream_epi_ahead<BF16, K, NB, UN, RB, OH, X3>() > 0 ? 6 * (size_t)NB * 32 * 4 : 0);   // + the views' affines
   if (lds > 160 * 1024) return TL_ERR_UNSUPPORTED;
   static TlAttrOnce attr_once;                     // per kernel instantiation AND device (the attribute is per device)
   if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_stream<BF16, K, NB, UN, DA, RB, OCC, OH, X3>), 160 * 1024)) return TL_ERR_LAUNCH;

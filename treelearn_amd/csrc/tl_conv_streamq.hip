@@ -53,6 +53,16 @@ static __device__ __forceinline__ void quad_transpose(const u32x4 (&S)[4], u32x4
     }
 }
 
+// Which epilogue an instantiation's inference launches take (tl_conv_internal.h): the number of 32 x 32 blocks whose residual rows are requested
+// ahead of the first store (epi_wave_tail_lds, affines from an LDS copy), or 0 = the per-view loads of epi_block32 only.  Named by shape:
+//   the 8-tap 64 -> 96 kernel (level 2 -> 3 strided conv) sits at 126 registers -- four waves per SIMD -- and the LDS form's few extra
+//   registers cost it the fourth wave: it stays on the per-view loads.
+template <int K, int NB, int PN, int RB, bool X3>
+constexpr int streamq_epi_ahead() {
+  constexpr bool strided_64_96 = K == 8 && NB == 3 && PN == 1;
+  return strided_64_96 ? 0 : epi_pd<!X3>(RB * NB);
+}
+
 // W waves per workgroup, each owning RB blocks of 32 rows (one weight fragment read from LDS feeds RB MFMAs).
 // SP: the input channels are walked in SP slices of PN * 64: step v of the K * SP steps contracts slice v % SP of tap v / SP
 // (same registers and LDS as the PN-wide kernel; 256 -> 128 as SP = 2 x 128 instead of a PN = 4 kernel that spills).
@@ -78,6 +88,9 @@ __global__ void __launch_bounds__(W * 64, OCC) k_conv_streamq(ConvP p) {
   char* Bs = smem;                                                          // [2][COUT][BROW]
   int* Is = reinterpret_cast<int*>(smem + WB);                              // [W][K][RB][8][4] row indices
   float* Es = reinterpret_cast<float*>(smem);                               // epilogue alias: [W][32][EP]
+  constexpr int PD = streamq_epi_ahead<K, NB, PN, RB, X3>();
+  constexpr int TAPB = WB + W * K * WROWS * 4, EPB = W * 32 * EP * 4;
+  [[maybe_unused]] float* Af = reinterpret_cast<float*>(smem + (TAPB > EPB ? TAPB : EPB));   // PD > 0: [3][2][COUT] the views' affines (epi_aff_put), live to the end
 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int fi = lane & 31, fh = lane >> 5;
@@ -85,6 +98,9 @@ __global__ void __launch_bounds__(W * 64, OCC) k_conv_streamq(ConvP p) {
   const int tile = xcd_tile(blockIdx.x, p.nblk);
   const int64_t r0 = (int64_t)tile * (W * WROWS) + wv * WROWS;
 
+  static_assert(COUT <= NTH, "one affine element per thread");
+  [[maybe_unused]] EpiAffRegs afr = {};
+  if constexpr (PD > 0) afr = epi_aff_fetch(p, tid, COUT);    // requested ahead of the rulebook, parked behind it
   // the wave's slice of the rulebook -> LDS, [k][rb][row & 7][row >> 3]
   int* iw = Is + wv * (K * WROWS);
 #pragma unroll
@@ -110,6 +126,7 @@ __global__ void __launch_bounds__(W * 64, OCC) k_conv_streamq(ConvP p) {
       if (k < K) iw[((k * RB + rb) * 8 + (fi & 7)) * 4 + (fi >> 3)] = v[t];
     }
   }
+  if constexpr (PD > 0) epi_aff_put(afr, Af, tid, COUT);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
 
@@ -268,6 +285,12 @@ __global__ void __launch_bounds__(W * 64, OCC) k_conv_streamq(ConvP p) {
   }
 
   // epilogue: MFMA row m = (r & 3) + 8 (r >> 2) + 4 fh is tile row rho(m) = ((m >> 2) & 7) + 8 (m & 3) = 2 (r >> 2) + fh + 8 (r & 3)
+  if constexpr (PD > 0) {
+    if (p.epi_mode == TL_EPI_NONE) {                 // inference: affines from LDS, residual ahead, stores back to back (workgroup-uniform)
+      epi_wave_tail_lds<!X3, W, EP, NB, RB, true, PD>(p, Es, Af, tid, r0, acc);
+      return;
+    }
+  }
   __syncthreads();
   float* ew = Es + wv * 32 * EP;
   float red0[NB], red1[NB];
@@ -293,7 +316,7 @@ int launch(ConvP p, hipStream_t s) {
   constexpr int OCC = 2;
   if constexpr (X3) p.w = p.w_x3;
   const size_t wt = 2 * (size_t)NB * 32 * (PN * 128 + 16) + (size_t)W * K * 32 * RB * 4, ep = (size_t)W * 32 * 36 * 4;
-  const size_t lds = wt > ep ? wt : ep;
+  const size_t lds = (wt > ep ? wt : ep) + (streamq_epi_ahead<K, NB, PN, RB, X3>() > 0 ? 6 * (size_t)NB * 32 * 4 : 0);   // + the views' affines
   if (lds > 160 * 1024) return TL_ERR_UNSUPPORTED;
   static TlAttrOnce attr_once;                     // per kernel instantiation AND device (the attribute is per device)
   if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_streamq<K, NB, PN, DA, W, RB, OCC, SP, X3, UL>), 160 * 1024)) return TL_ERR_LAUNCH;
