@@ -287,6 +287,13 @@ typedef struct tl_conv_args {
 int64_t tl_conv_red_parts(int64_t n_out);
 
 int tl_conv_fwd(const tl_conv_args* args, tl_stream_t stream);
+/* Which kernel(s) tl_conv_fwd would launch for `args`, without a GPU: runs the very same dispatch with every launch replaced by a record
+ * "k_name<template args><<<grid, block, dynamic LDS bytes>>>" ("/f16" after the name: the float16 compilation of the kernel), records of a
+ * conv that is two launches joined by " + ", written to buf (NUL-terminated, at most cap bytes).  Makes no HIP call and reads no memory
+ * behind the pointers in `args` (any suitably aligned non-NULL value serves) except the host pointer red_nparts, which is written as by
+ * tl_conv_fwd.  Returns what tl_conv_fwd would have returned (an empty route when that is an error), TL_ERR_ARG if the route did not fit.
+ * Honours tl_set_tuning.  Per thread: another thread's tl_conv_fwd launches as usual meanwhile. */
+int tl_conv_route(const tl_conv_args* args, char* buf, int cap);
 
 /* Repack a reference-layout conv weight [Cout, k,k,k, Cin] (spconv `.weight`)
  * into the kernel layout [K=k^3][Cout][Cin] with dtype conversion. */

@@ -24,14 +24,18 @@ SENT = -1024.0                      # exact in every dtype
 H16 = (torch.bfloat16, torch.float16)
 ALL = (torch.bfloat16, torch.float16, torch.float32)
 
-# (family the dispatch serves the shape with, Cin, Cout, K, rulebook kind, small-level threshold left on, dtypes)
+# (family the dispatch serves the shape with -- asserted through ops.conv_route: the label's first word names the kernel, KERNEL_OF --,
+#  Cin, Cout, K, rulebook kind, small-level threshold left on, dtypes)
+KERNEL_OF = {"stream-q": "k_conv_streamq", "stream": "k_conv_stream", "direct": "k_conv_direct", "k_conv_up": "k_conv_up", "small-level": "k_conv_small",
+             "k_conv_bf16": "k_conv_bf16"}
 FAMILIES = [
     ("stream-q 64->64", 64, 64, 27, "table", False, H16),
     ("stream-q 128->64", 128, 64, 27, "table", False, H16),
     ("stream-q 192->96", 192, 96, 27, "table", False, H16),
     ("stream-q 128->128", 128, 128, 27, "table", False, H16),
     ("stream 96->96", 96, 96, 27, "table", False, ALL),
-    ("stream / direct strided 32->64", 32, 64, 8, "table", False, ALL),
+    ("stream strided 32->64", 32, 64, 8, "table", False, H16),
+    ("direct strided 32->64", 32, 64, 8, "table", False, (torch.float32,)),
     ("direct 1x1 128->64", 128, 64, 1, "none", False, ALL),
     ("direct one-hot inverse 64->32", 64, 32, 8, "one_hot", False, H16),
     ("k_conv_up 96->64", 96, 64, 8, "up", False, H16),
@@ -116,6 +120,10 @@ def _launch(ops, x, w, tab, n_out, specs, cout, dtype, d, **kw):
     extra = {}
     for name, (buf, view), s in zip(("out2", "out3"), bufs[1:], specs[1:]):
         extra[name] = (view, s[0], s[1], s[2])
+    kernel = kw.pop("kernel", None)
+    if kernel is not None:                                    # the family under test is the one the dispatch serves these very arguments with
+        route = ops.conv_route(x, w, tab, n_out, out=bufs[0][1], out_scale=s0[0], out_shift=s0[1], out_relu=s0[2], **extra, **kw)
+        assert route.startswith(kernel + "<") and ("/f16<<<" in route) == (dtype == torch.float16), (kernel, route)
     ops.conv_fwd(x, w, tab, n_out, out=bufs[0][1], out_scale=s0[0], out_shift=s0[1], out_relu=s0[2], **extra, **kw)
     for buf, _ in bufs:
         assert _intact(buf, n_out, cout), "a store outside the n_out x C destination"
@@ -171,7 +179,7 @@ def _run_family(fam, dtype, tol, x3):
             resbuf[:, :cout] = torch.from_numpy(res64).to(d).to(dtype)
             res = resbuf[:, :cout]
             tab = None if table is None else torch.from_numpy(np.ascontiguousarray(table.T)).to(d)
-            kw = {}
+            kw = {"kernel": KERNEL_OF[name.split()[0]]}
             if kind in ("one_hot", "up"):
                 kw["one_hot"] = True
             if scatter is not None:

@@ -128,6 +128,7 @@ PROTOTYPES = {
     "tl_blk_ws_words": (_i64, [_I4]),
     "tl_blk_build": (_i32, [_vp, _vp, _I4, _i64, _c.POINTER(Blk), _vp, _i32, _vp]),
     "tl_conv_fwd": (_i32, [_c.POINTER(ConvArgs), _vp]),
+    "tl_conv_route": (_i32, [_c.POINTER(ConvArgs), _c.c_char_p, _i32]),
     "tl_conv_red_parts": (_i64, [_i64]),
     "tl_exec_create": (_vp, []),
     "tl_exec_destroy": (None, [_vp]),

@@ -257,10 +257,7 @@ int launch_b(const ConvP& p, hipStream_t s) {
   const size_t epi_b = 4 * (size_t)32 * (NB * 32 + 4) * 4;
   const size_t lds = (size_t)p.K * TM * 4 + 128 + (size_t)p.Cin * 8 + (main_b > epi_b ? main_b : epi_b);
   if (lds > 160 * 1024) return TL_ERR_UNSUPPORTED;
-  static TlAttrOnce attr_once;                     // per kernel instantiation AND device (the attribute is per device)
-  if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_bf16<NB, U, D, BUF>), 160 * 1024)) return TL_ERR_LAUNCH;
-  k_conv_bf16<NB, U, D, BUF><<<p.nblk, 256, lds, s>>>(p);
-  return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
+  return tl_launch_lds<k_conv_bf16<NB, U, D, BUF>>(p.nblk, 256, lds, s, p);
 }
 
 template <int NB, int U, int D>
@@ -276,7 +273,7 @@ int launch(const ConvP& p, hipStream_t s) {
 // Requirements (checked by the caller): Cin % 32 == 0, Cout % 32 == 0, Cout <= 224, 16-B aligned rows
 // (in_ld, out_ld, res_ld multiples of 8; base pointers 16-B aligned).
 // Two units per step, prefetch depth 2 (measured: depth 2 >= 3 (occupancy) >= 1 on the config-2 levels).
-int tl_launch_conv_bf16(const ConvP& p, hipStream_t s) {
+int TL_H16(tl_launch_conv_bf16)(const ConvP& p, hipStream_t s) {
   switch (p.Cout / 32) {
     case 1: return launch<1, 2, 2>(p, s);
     case 2: return launch<2, 2, 2>(p, s);

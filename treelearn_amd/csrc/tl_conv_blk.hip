@@ -434,18 +434,15 @@ template <int W, bool RES, int NV, bool TR = false, bool PRO = false>
 int launch_blk(const ConvP& p, hipStream_t s) {
   constexpr size_t lds = (size_t)WS_B + AFF_B + (size_t)W * STAGE_B + (TR ? (size_t)W * 2 * 32 * 8 : 0);
   static_assert(lds <= 160 * 1024, "LDS budget");
-  static TlAttrOnce attr_once;                     // per kernel instantiation AND device (the attribute is per device)
-  if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_blk<W, RES, NV, TR, PRO>), 160 * 1024)) return TL_ERR_LAUNCH;
-  k_conv_blk<W, RES, NV, TR, PRO><<<256, W * 64, lds, s>>>(p);
   if (TR && p.red_nparts) *p.red_nparts = 256;
-  return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
+  return tl_launch_lds<k_conv_blk<W, RES, NV, TR, PRO>>(256, W * 64, lds, s, p);
 }
 
 }  // namespace
 
 // 27 taps, 32 -> 32 channels, 16-bit, rows in the block-local order with the staged rulebook of tl_blk_build; no gather-side prologue, no
 // training epilogue.  Every view 16-B aligned with a row stride that is a multiple of 8 elements; buffers below 4 GB.
-int tl_launch_conv_blk(const ConvP& p, hipStream_t s) {
+int TL_H16(tl_launch_conv_blk)(const ConvP& p, hipStream_t s) {
   if (!p.blk_unit || !p.blk_counter || !p.blk_halo || !p.blk_lrb) return TL_ERR_UNSUPPORTED;
   if (p.K != 27 || p.Cin != 32 || p.Cout != 32 || p.n_in != p.n_out) return TL_ERR_UNSUPPORTED;
   const bool pro = p.in_scale || p.in_relu;

@@ -373,10 +373,7 @@ template <int W, bool RES, int NV>
 int launch_x3(const ConvP& p, const X3P& xp, hipStream_t s) {
   constexpr size_t lds = (size_t)WS_B + AFF_B + (size_t)W * STAGE_B;
   static_assert(lds <= 160 * 1024, "LDS budget");
-  static TlAttrOnce attr_once;                     // per kernel instantiation AND device (the attribute is per device)
-  if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_blk_x3<W, RES, NV>), 160 * 1024)) return TL_ERR_LAUNCH;
-  k_conv_blk_x3<W, RES, NV><<<256, W * 64, lds, s>>>(p, xp);
-  return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
+  return tl_launch_lds<k_conv_blk_x3<W, RES, NV>>(256, W * 64, lds, s, p, xp);
 }
 
 }  // namespace

@@ -482,16 +482,13 @@ int launch(const ConvP& p_, hipStream_t s) {
   constexpr int UB = BF16 ? 64 : 128;
   const size_t lds = (size_t)K * UN * NB * 32 * UB + (size_t)WAVES * 32 * (NB * 32 + 4) * 4 + (TR ? (size_t)WAVES * 2 * NB * 32 * 8 : 0);
   if (lds > 160 * 1024) return TL_ERR_UNSUPPORTED;
-  static TlAttrOnce attr_once;                     // per kernel instantiation AND device (the attribute is per device)
-  if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_direct<BF16, K, NB, UN, G, WAVES, CT, TR, OH, X3>), 160 * 1024)) return TL_ERR_LAUNCH;
   const int ntiles = (int)tl_cdiv(p.n_out, 32);
   const int per_cu = (int)((160 * 1024) / lds) < 1 ? 1 : (int)((160 * 1024) / lds);
   int grid = 256 * (per_cu > 2 ? 2 : per_cu);
   const int need = (int)tl_cdiv(ntiles, WAVES);
   if (grid > need) grid = need;
-  k_conv_direct<BF16, K, NB, UN, G, WAVES, CT, TR, OH, X3><<<grid, WAVES * 64, lds, s>>>(p, ntiles, 0);
   if (p.red_nparts) *p.red_nparts = grid;
-  return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
+  return tl_launch_lds<k_conv_direct<BF16, K, NB, UN, G, WAVES, CT, TR, OH, X3>>(grid, WAVES * 64, lds, s, p, ntiles, 0);
   }
 }
 
@@ -547,17 +544,17 @@ int dispatch(const ConvP& p, hipStream_t s) {
 }  // namespace
 
 // all-ones input (tl_conv_args.in_all_ones): bf16, K = 27 with the column-form rulebook, Cout = 32
-int tl_launch_conv_ones27(const ConvP& p, int dtype, hipStream_t s) {
+int TL_H16(tl_launch_conv_ones27)(const ConvP& p, int dtype, hipStream_t s) {
   if (p.K != 27 || p.Cout != 32 || (!p.ctab && !p.blk_pmask) || p.Cin <= 0 || p.Cin > 64 || p.in_scale || p.in_relu || p.epi_mode != TL_EPI_NONE) return TL_ERR_UNSUPPORTED;
-  if (dtype == TL_BF16) k_conv_ones27<true><<<tl_grid(p.n_out * 4, 256), 256, 0, s>>>(p);
-  else k_conv_ones27<false><<<tl_grid(p.n_out * 4, 256), 256, 0, s>>>(p);          // fp32 storage (the exact and the bf16x3 parity modes)
-  return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
+  const unsigned g = tl_grid(p.n_out * 4, 256);
+  if (dtype == TL_BF16) return tl_launch<k_conv_ones27<true>>(g, 256, 0, s, p);
+  return tl_launch<k_conv_ones27<false>>(g, 256, 0, s, p);                         // fp32 storage (the exact and the bf16x3 parity modes)
 }
 
 
 // Eligibility (beyond the tile kernel's alignment rules): no gather-side prologue, whole weight tensor + epilogue
 // scratch within LDS, input view below 4 GB.  Returns TL_ERR_UNSUPPORTED when the shape is not covered.
-int tl_launch_conv_direct(const ConvP& p, int dtype, hipStream_t s) {
+int TL_H16(tl_launch_conv_direct)(const ConvP& p, int dtype, hipStream_t s) {
   if (p.in_scale || p.in_relu) return TL_ERR_UNSUPPORTED;
   if (p.one_hot == 2 && !(p.K == 8 && p.Cin == 64 && p.Cout == 32 && p.epi_mode == TL_EPI_NONE && (dtype == TL_BF16 || p.w_x3))) return TL_ERR_UNSUPPORTED;
   const int eb = dtype == TL_BF16 ? 2 : 4;
@@ -565,13 +562,10 @@ int tl_launch_conv_direct(const ConvP& p, int dtype, hipStream_t s) {
     const int ntiles = (int)tl_cdiv(p.n_out, 32);
     int grid = (int)tl_cdiv(ntiles, 8);
     if (grid > 2048) grid = 2048;
-    if (p.epi_mode != TL_EPI_NONE) {
-      if (p.ctab && p.K == 27) k_conv_in4<8, true, true><<<grid, 512, 0, s>>>(p, ntiles);
-      else k_conv_in4<8, false, true><<<grid, 512, 0, s>>>(p, ntiles);
-    } else if (p.ctab && p.K == 27) k_conv_in4<8, true><<<grid, 512, 0, s>>>(p, ntiles);
-    else k_conv_in4<8><<<grid, 512, 0, s>>>(p, ntiles);
     if (p.red_nparts) *p.red_nparts = grid;
-    return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
+    const bool ct = p.ctab && p.K == 27;
+    if (p.epi_mode != TL_EPI_NONE) return ct ? tl_launch<k_conv_in4<8, true, true>>(grid, 512, 0, s, p, ntiles) : tl_launch<k_conv_in4<8, false, true>>(grid, 512, 0, s, p, ntiles);
+    return ct ? tl_launch<k_conv_in4<8, true>>(grid, 512, 0, s, p, ntiles) : tl_launch<k_conv_in4<8>>(grid, 512, 0, s, p, ntiles);
   }
   if (p.Cin % 32 || p.Cout % 32) return TL_ERR_UNSUPPORTED;
   const int64_t ld_b = p.in_ld * eb, in_bytes = (p.n_in - 1) * ld_b + (int64_t)p.Cin * eb;

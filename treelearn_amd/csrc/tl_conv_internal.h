@@ -4,23 +4,21 @@
 #include <hip/hip_bf16.h>
 #include "tl_half.h"
 
-#ifdef TL_F16_BUILD       // the float16 build of the conv units: same sources, IEEE-half conversions (tl_half.h), launchers with an _f16 suffix
-#define tl_launch_conv_direct tl_launch_conv_direct_f16
-#define tl_launch_conv_ones27 tl_launch_conv_ones27_f16
-#define tl_launch_conv_stream tl_launch_conv_stream_f16
-#define tl_launch_conv_streamq tl_launch_conv_streamq_f16
-#define tl_launch_conv_small tl_launch_conv_small_f16
-#define tl_launch_conv_tinycin tl_launch_conv_tinycin_f16
-#define tl_launch_conv_bf16 tl_launch_conv_bf16_f16
-#define tl_launch_conv_blk tl_launch_conv_blk_f16
-#define tl_launch_conv_up tl_launch_conv_up_f16
+// The float16 build of the conv units (build.py F16_UNITS): the same sources with IEEE-half conversions (tl_half.h).  A unit defines its
+// launchers as `int TL_H16(tl_launch_conv_x)(...)`: the plain name in the bf16 build, the name with an _f16 suffix in the float16 one.
+#ifdef TL_F16_BUILD
+#define TL_H16(name) name##_f16
 #define g_small_mode g_small_mode_f16
+#else
+#define TL_H16(name) name
 #endif
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int TL_CONV_TILE_ROWS = 128;   // rows per workgroup of the two tile kernels (tl_conv_bf16.hip, tl_conv_fallback.hip): ConvP.nblk as tl_conv_fwd fills it
 
 struct ConvP {
   const void* in; int64_t in_ld;
@@ -458,45 +456,39 @@ static __device__ __forceinline__ void decode_ctab(const int32_t* __restrict__ c
   }
 }
 
-// tl_conv_bf16.hip
-int tl_launch_conv_bf16(const ConvP& p, hipStream_t s);   // large levels, bf16 MFMA
+// ---- the launchers.  Every one returns TL_ERR_UNSUPPORTED (nothing launched) for a shape its family has no kernel for.
+// The families that exist once per 16-bit type, as ONE list: X(family, parameters).  It declares tl_launch_conv_<family> (bf16 build) and
+// tl_launch_conv_<family>_f16 (float16 build) and is the member list of TlConvH16, of which tl_conv_fwd picks kTlConvBf16 or kTlConvF16.
+// Inside the float16 units -- and in the dispatch -- dtype TL_BF16 means "the 16-bit type".
+#define TL_CONV_H16_FAMILIES(X)                                                                                                                 \
+  X(direct, (const ConvP& p, int dtype, hipStream_t s))          /* tl_conv_direct.hip: whole weight tensor resident in LDS, per-wave tiles */   \
+  X(ones27, (const ConvP& p, int dtype, hipStream_t s))          /* ... every input element is 1: presence-mask table, no gather */               \
+  X(up, (const ConvP& p, const int32_t* child, hipStream_t s))   /* tl_conv_up.hip: 16-bit inverse conv, coarse-stationary scatter form */        \
+  X(blk, (const ConvP& p, hipStream_t s))                        /* tl_conv_blk.hip: 16-bit, 27 taps, 32 -> 32: rows in block-local order, staged units */ \
+  X(stream, (const ConvP& p, int dtype, hipStream_t s))          /* tl_conv_stream.hip: per-wave register gathers, weights streamed through LDS per tap */ \
+  X(streamq, (const ConvP& p, hipStream_t s))                    /* tl_conv_streamq.hip: 16-bit, Cin % 64 == 0: quad-coalesced gathers + register transposition */ \
+  X(small, (const ConvP& p, int dtype, hipStream_t s))           /* tl_conv_small.hip: few output rows: split the tap loop over waves */          \
+  X(tinycin, (const ConvP& p, int dtype, hipStream_t s))         /* ... Cin <= 8 (the 4-channel input conv) */                                    \
+  X(bf16, (const ConvP& p, hipStream_t s))                       /* tl_conv_bf16.hip: large levels, 16-bit MFMA tile kernel */
 
-// tl_conv_direct.hip
-int tl_launch_conv_direct(const ConvP& p, int dtype, hipStream_t s);   // whole weight tensor resident in LDS, per-wave tiles
-int tl_launch_conv_ones27(const ConvP& p, int dtype, hipStream_t s);               // every input element is 1: presence-mask table, no gather
+#define TL_X(family, params) int tl_launch_conv_##family params; int tl_launch_conv_##family##_f16 params;
+TL_CONV_H16_FAMILIES(TL_X)
+#undef TL_X
+struct TlConvH16 {
+#define TL_X(family, params) int (*family) params;
+  TL_CONV_H16_FAMILIES(TL_X)
+#undef TL_X
+};
+#define TL_X(family, params) tl_launch_conv_##family,
+constexpr TlConvH16 kTlConvBf16 = {TL_CONV_H16_FAMILIES(TL_X)};
+#undef TL_X
+#define TL_X(family, params) tl_launch_conv_##family##_f16,
+constexpr TlConvH16 kTlConvF16 = {TL_CONV_H16_FAMILIES(TL_X)};
+#undef TL_X
 
-// tl_conv_up.hip
-int tl_launch_conv_up(const ConvP& p, const int32_t* child, hipStream_t s);   // 16-bit inverse conv, coarse-stationary scatter form
-
-// tl_conv_blk.hip
-int tl_launch_conv_blk(const ConvP& p, hipStream_t s);                  // 16-bit, 27 taps, 32 -> 32: rows in block-local order, staged units
-#ifndef TL_F16_BUILD
-int tl_launch_conv_blk_x3(const ConvP& p, hipStream_t s);               // fp32 rows, split-bf16 contraction (bf16x3), 27 taps, 32 -> 32: staged units, two 16-channel launches
-int tl_launch_conv_streamq_x3(const ConvP& p, hipStream_t s);                   // fp32 rows, split-bf16 contraction: quad-coalesced gathers (levels 2-3)
-#endif
-
-// tl_conv_stream.hip
-int tl_launch_conv_stream(const ConvP& p, int dtype, hipStream_t s);   // per-wave register gathers, weights streamed through LDS per tap
-
-// tl_conv_streamq.hip
-int tl_launch_conv_streamq(const ConvP& p, hipStream_t s);              // bf16, Cin % 64 == 0: quad-coalesced gathers + register transposition
-
-// tl_conv_small.hip
-int tl_launch_conv_small(const ConvP& p, int dtype, hipStream_t s);     // few output rows: split the tap loop over waves
-int tl_launch_conv_tinycin(const ConvP& p, int dtype, hipStream_t s);   // Cin <= 8 (the 4-channel input conv)
-
-#ifndef TL_F16_BUILD
-// the float16 compilations of the same units (tl_half.h): inside them dtype TL_BF16 means "the 16-bit type"
-int tl_launch_conv_direct_f16(const ConvP& p, int dtype, hipStream_t s);
-int tl_launch_conv_ones27_f16(const ConvP& p, int dtype, hipStream_t s);
-int tl_launch_conv_stream_f16(const ConvP& p, int dtype, hipStream_t s);
-int tl_launch_conv_streamq_f16(const ConvP& p, hipStream_t s);
-int tl_launch_conv_small_f16(const ConvP& p, int dtype, hipStream_t s);
-int tl_launch_conv_tinycin_f16(const ConvP& p, int dtype, hipStream_t s);
-int tl_launch_conv_bf16_f16(const ConvP& p, hipStream_t s);
-int tl_launch_conv_blk_f16(const ConvP& p, hipStream_t s);
-int tl_launch_conv_up_f16(const ConvP& p, const int32_t* child, hipStream_t s);
-#endif
-
-// tl_linear_small.hip
-int tl_launch_conv_tinycout(const ConvP& p, int dtype, hipStream_t s);  // K = 1, Cout <= 8 (the heads' output Linears)
+// compiled once (fp32 rows)
+int tl_launch_conv_blk_x3(const ConvP& p, hipStream_t s);               // tl_conv_blk_x3.hip: fp32 rows, split-bf16 contraction (bf16x3), 27 taps, 32 -> 32: staged units, two 16-channel launches
+int tl_launch_conv_streamq_x3(const ConvP& p, hipStream_t s);           // tl_conv_streamq.hip: fp32 rows, split-bf16 contraction: quad-coalesced gathers (levels 2-3)
+int tl_launch_conv_mfma_f32(const ConvP& p, hipStream_t s);             // tl_conv_fallback.hip: exact fp32 tile kernel, Cout <= 224
+int tl_launch_conv_generic(const ConvP& p, int dtype, hipStream_t s);   // ... scalar, any shape, TL_F32 / TL_BF16
+int tl_launch_conv_tinycout(const ConvP& p, int dtype, hipStream_t s);  // tl_linear_small.hip: K = 1, Cout <= 8 (the heads' output Linears)

@@ -211,24 +211,31 @@ int launch_tiny(const ConvP& p, hipStream_t s) {
   const size_t lds = (size_t)p.K * p.Cin * p.Cout * 4;
   const unsigned g = tl_grid(p.n_out * (p.Cout / 8), 256);
   switch (p.Cin) {
-    case 1: k_conv_tinycin<T, 1><<<g, 256, lds, s>>>(p); break;
-    case 2: k_conv_tinycin<T, 2><<<g, 256, lds, s>>>(p); break;
-    case 3: k_conv_tinycin<T, 3><<<g, 256, lds, s>>>(p); break;
-    case 4: k_conv_tinycin<T, 4><<<g, 256, lds, s>>>(p); break;
-    case 5: k_conv_tinycin<T, 5><<<g, 256, lds, s>>>(p); break;
-    case 6: k_conv_tinycin<T, 6><<<g, 256, lds, s>>>(p); break;
-    case 7: k_conv_tinycin<T, 7><<<g, 256, lds, s>>>(p); break;
-    case 8: k_conv_tinycin<T, 8><<<g, 256, lds, s>>>(p); break;
-    default: return TL_ERR_UNSUPPORTED;
+    case 1: return tl_launch<k_conv_tinycin<T, 1>>(g, 256, lds, s, p);
+    case 2: return tl_launch<k_conv_tinycin<T, 2>>(g, 256, lds, s, p);
+    case 3: return tl_launch<k_conv_tinycin<T, 3>>(g, 256, lds, s, p);
+    case 4: return tl_launch<k_conv_tinycin<T, 4>>(g, 256, lds, s, p);
+    case 5: return tl_launch<k_conv_tinycin<T, 5>>(g, 256, lds, s, p);
+    case 6: return tl_launch<k_conv_tinycin<T, 6>>(g, 256, lds, s, p);
+    case 7: return tl_launch<k_conv_tinycin<T, 7>>(g, 256, lds, s, p);
+    case 8: return tl_launch<k_conv_tinycin<T, 8>>(g, 256, lds, s, p);
   }
-  return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
+  return TL_ERR_UNSUPPORTED;
+}
+
+// one (dtype, weight form) of the small-level kernel in its three workgroup shapes: 8 waves x one 32-column block, 4 waves x two, 4 waves x one
+template <bool BF, bool FR, bool X3 = false>
+int launch_small(int form, unsigned g, int ncb, const ConvP& p, hipStream_t s) {
+  if (form == 8) return tl_launch<k_conv_small<BF, 1, 8, FR, X3>>(g, 512, 0, s, p, ncb);
+  if (form == 2) return tl_launch<k_conv_small<BF, 2, 4, FR, X3>>(g, 256, 0, s, p, ncb);
+  return tl_launch<k_conv_small<BF, 1, 4, FR, X3>>(g, 256, 0, s, p, ncb);
 }
 
 }  // namespace
 
 int g_small_mode = 0;   // developer A/B (tl_set_tuning "small_mode"): 0 = by size, 1 = always 4 waves (no full-width blocks), 2 = always 8 waves x 32 columns, 3 = ignore the fragment-order weights
 
-int tl_launch_conv_small(const ConvP& p, int dtype, hipStream_t s) {
+int TL_H16(tl_launch_conv_small)(const ConvP& p, int dtype, hipStream_t s) {
   const int nrt = (int)tl_cdiv(p.n_out, 32);
   // few row tiles: 8 waves split the (tap, chunk) steps of a 32 x 32 output block (more, shorter dependent chains);
   // otherwise 4 waves per 32 x 64 (or 32 x 32) block
@@ -243,41 +250,25 @@ int tl_launch_conv_small(const ConvP& p, int dtype, hipStream_t s) {
                     ((uintptr_t)p.w_frag) % 16 == 0;
   if (full) {
     switch (cbt) {
-      case 3: k_conv_small<true, 3, 4, true><<<nrt, 256, 0, s>>>(p, 1); break;
-      case 5: k_conv_small<true, 5, 4, true><<<nrt, 256, 0, s>>>(p, 1); break;
-      case 7: k_conv_small<true, 7, 4, true><<<nrt, 256, 0, s>>>(p, 1); break;
+      case 3: return tl_launch<k_conv_small<true, 3, 4, true>>(nrt, 256, 0, s, p, 1);
+      case 5: return tl_launch<k_conv_small<true, 5, 4, true>>(nrt, 256, 0, s, p, 1);
+      case 7: return tl_launch<k_conv_small<true, 7, 4, true>>(nrt, 256, 0, s, p, 1);
     }
-    return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
   }
   const bool two = !eight && (p.Cout % 64 == 0);
   const int ncb = p.Cout / (two ? 64 : 32);
   const unsigned g = (unsigned)(nrt * ncb);
-#define TL_SMALL(BF_, FR_)                                                                   \
-  do {                                                                                         \
-    if (eight) k_conv_small<BF_, 1, 8, FR_><<<g, 512, 0, s>>>(p, ncb);                         \
-    else if (two) k_conv_small<BF_, 2, 4, FR_><<<g, 256, 0, s>>>(p, ncb);                      \
-    else k_conv_small<BF_, 1, 4, FR_><<<g, 256, 0, s>>>(p, ncb);                               \
-  } while (0)
+  const int form = eight ? 8 : two ? 2 : 1;
   const bool fr = p.w_frag != nullptr && ((uintptr_t)p.w_frag) % 16 == 0 && g_small_mode != 3;
   // fp32 rows with split-bf16 weights (the bf16x3 mode; weights of >= 256 input channels come as two half-width convs: exact kernel)
   const bool x3 = dtype == TL_F32 && p.w_x3 != nullptr && p.Cin < 256 && !p.in_scale && !p.in_relu;
-  if (dtype == TL_BF16) { if (fr) TL_SMALL(true, true); else TL_SMALL(true, false); }
-  else if (x3 && g_small_mode != 3 && p.Cout % 32 == 0) {                        // (fragment-order copy of the split weights: 1 KB per load instead of 64 x 16 B)
-    if (eight) k_conv_small<false, 1, 8, true, true><<<g, 512, 0, s>>>(p, ncb);
-    else if (two) k_conv_small<false, 2, 4, true, true><<<g, 256, 0, s>>>(p, ncb);
-    else k_conv_small<false, 1, 4, true, true><<<g, 256, 0, s>>>(p, ncb);
-  }
-  else if (x3) {
-    if (eight) k_conv_small<false, 1, 8, false, true><<<g, 512, 0, s>>>(p, ncb);
-    else if (two) k_conv_small<false, 2, 4, false, true><<<g, 256, 0, s>>>(p, ncb);
-    else k_conv_small<false, 1, 4, false, true><<<g, 256, 0, s>>>(p, ncb);
-  }
-  else { if (fr) TL_SMALL(false, true); else TL_SMALL(false, false); }
-#undef TL_SMALL
-  return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
+  if (dtype == TL_BF16) return fr ? launch_small<true, true>(form, g, ncb, p, s) : launch_small<true, false>(form, g, ncb, p, s);
+  if (x3 && g_small_mode != 3 && p.Cout % 32 == 0) return launch_small<false, true, true>(form, g, ncb, p, s);   // (fragment-order copy of the split weights: 1 KB per load instead of 64 x 16 B)
+  if (x3) return launch_small<false, false, true>(form, g, ncb, p, s);
+  return fr ? launch_small<false, true>(form, g, ncb, p, s) : launch_small<false, false>(form, g, ncb, p, s);
 }
 
-int tl_launch_conv_tinycin(const ConvP& p, int dtype, hipStream_t s) {
+int TL_H16(tl_launch_conv_tinycin)(const ConvP& p, int dtype, hipStream_t s) {
   const bool out_ok = (dtype == TL_F32) ? (p.out_ld % 4 == 0 && ((uintptr_t)p.out) % 16 == 0) : (p.out_ld % 8 == 0 && ((uintptr_t)p.out) % 16 == 0);
   if (!out_ok) return TL_ERR_ARG;
   return dtype == TL_F32 ? launch_tiny<float>(p, s) : launch_tiny<__hip_bfloat16>(p, s);

@@ -259,12 +259,9 @@ int launch(ConvP p, hipStream_t s) {
   const size_t wt = 2 * (size_t)NB * 32 * (UN * 32 * EB + 16), ep = (size_t)WAVES * 32 * 36 * 4;
   const size_t lds = (wt > ep ? wt : ep) + (stream_epi_ahead<BF16, K, NB, UN, RB, OH, X3>() > 0 ? 6 * (size_t)NB * 32 * 4 : 0);   // + the views' affines
   if (lds > 160 * 1024) return TL_ERR_UNSUPPORTED;
-  static TlAttrOnce attr_once;                     // per kernel instantiation AND device (the attribute is per device)
-  if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_stream<BF16, K, NB, UN, DA, RB, OCC, OH, X3>), 160 * 1024)) return TL_ERR_LAUNCH;
   p.nblk = (int)tl_cdiv(p.n_out, WAVES * 32 * RB);
-  k_conv_stream<BF16, K, NB, UN, DA, RB, OCC, OH, X3><<<p.nblk, NT, lds, s>>>(p);
   if (p.red_nparts) *p.red_nparts = p.nblk;
-  return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
+  return tl_launch_lds<k_conv_stream<BF16, K, NB, UN, DA, RB, OCC, OH, X3>>(p.nblk, NT, lds, s, p);
 }
 
 template <bool BF16, int K>
@@ -308,7 +305,7 @@ int dispatch(const ConvP& p, hipStream_t s) {
 
 }  // namespace
 
-int tl_launch_conv_stream(const ConvP& p, int dtype, hipStream_t s) {
+int TL_H16(tl_launch_conv_stream)(const ConvP& p, int dtype, hipStream_t s) {
   if (p.in_scale || p.in_relu) return TL_ERR_UNSUPPORTED;
   const int eb = dtype == TL_BF16 ? 2 : 4;
   const int64_t ld_b = p.in_ld * eb, in_bytes = (p.n_in - 1) * ld_b + (int64_t)p.Cin * eb;

@@ -318,17 +318,14 @@ int launch(ConvP p, hipStream_t s) {
   const size_t wt = 2 * (size_t)NB * 32 * (PN * 128 + 16) + (size_t)W * K * 32 * RB * 4, ep = (size_t)W * 32 * 36 * 4;
   const size_t lds = (wt > ep ? wt : ep) + (streamq_epi_ahead<K, NB, PN, RB, X3>() > 0 ? 6 * (size_t)NB * 32 * 4 : 0);   // + the views' affines
   if (lds > 160 * 1024) return TL_ERR_UNSUPPORTED;
-  static TlAttrOnce attr_once;                     // per kernel instantiation AND device (the attribute is per device)
-  if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_streamq<K, NB, PN, DA, W, RB, OCC, SP, X3, UL>), 160 * 1024)) return TL_ERR_LAUNCH;
   p.nblk = (int)tl_cdiv(p.n_out, W * 32 * RB);
-  k_conv_streamq<K, NB, PN, DA, W, RB, OCC, SP, X3, UL><<<p.nblk, W * 64, lds, s>>>(p);
   if (p.red_nparts) *p.red_nparts = p.nblk;
-  return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
+  return tl_launch_lds<k_conv_streamq<K, NB, PN, DA, W, RB, OCC, SP, X3, UL>>(p.nblk, W * 64, lds, s, p);
 }
 
 }  // namespace
 
-int tl_launch_conv_streamq(const ConvP& p, hipStream_t s) {
+int TL_H16(tl_launch_conv_streamq)(const ConvP& p, hipStream_t s) {
   if (p.in_scale || p.in_relu || p.Cin % 64 || p.Cout % 32) return TL_ERR_UNSUPPORTED;
   const int64_t ld_b = p.in_ld * 2, in_bytes = (p.n_in - 1) * ld_b + (int64_t)p.Cin * 2;
   if (!(in_bytes > 0 && in_bytes + 2 * ld_b < 0xFFFFFFFFll)) return TL_ERR_UNSUPPORTED;

@@ -106,22 +106,19 @@ template <int NBI, int NBO, int WAVES>
 int launch_up(const ConvP& p, const int32_t* child, hipStream_t s) {
   const size_t lds = (size_t)8 * NBO * NBI * 2 * 1024 + (size_t)WAVES * 32 * 36 * 4;
   static_assert(8 * NBO * NBI * 2 * 1024 + WAVES * 32 * 36 * 4 <= 160 * 1024, "weights + epilogue tiles must fit the LDS");
-  static TlAttrOnce attr_once;                     // per kernel instantiation AND device (the attribute is per device)
-  if (!tl_lds_attr(attr_once, reinterpret_cast<const void*>(&k_conv_up<NBI, NBO, WAVES>), 160 * 1024)) return TL_ERR_LAUNCH;
   const int ntiles = (int)tl_cdiv(p.n_in, 32);
   const int per_cu = (int)((160 * 1024) / lds) < 1 ? 1 : (int)((160 * 1024) / lds);
   int grid = 256 * (per_cu > 4 ? 4 : per_cu);
   const int need = (int)tl_cdiv(ntiles, WAVES);
   if (grid > need) grid = need;
-  k_conv_up<NBI, NBO, WAVES><<<grid, WAVES * 64, lds, s>>>(p, child, ntiles);
-  return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
+  return tl_launch_lds<k_conv_up<NBI, NBO, WAVES>>(grid, WAVES * 64, lds, s, p, child, ntiles);
 }
 
 }  // namespace
 
 // Eligibility beyond tl_conv_fwd's alignment rules: 16-bit, K = 8, the one-hot table's scatter form given, fragment-order weights, no
 // gather-side prologue, no residual, inference epilogues; 32-bit byte offsets.
-int tl_launch_conv_up(const ConvP& p, const int32_t* child, hipStream_t s) {
+int TL_H16(tl_launch_conv_up)(const ConvP& p, const int32_t* child, hipStream_t s) {
   if (!child || !p.w_frag || ((uintptr_t)p.w_frag) % 16 || p.K != 8 || p.in_scale || p.in_relu || p.res || p.epi_mode != TL_EPI_NONE) return TL_ERR_UNSUPPORTED;
   auto big = [&](int64_t rows, int64_t ld) { return (rows - 1) * ld * 2 + 512 >= 0x7FFFFFFFll; };
   if (big(p.n_in, p.in_ld) || big(p.n_out, p.out_ld) || (p.out2 && big(p.n_out, p.out2_ld)) || (p.out3 && big(p.n_out, p.out3_ld)) || (int64_t)8 * p.n_in * 4 >= 0x7FFFFFFFll)

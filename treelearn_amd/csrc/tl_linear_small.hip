@@ -103,14 +103,12 @@ int tl_launch_conv_tinycout(const ConvP& p, int dtype, hipStream_t s) {
   if (p.in_ld % 8 || ((uintptr_t)p.in) % 16 || ((uintptr_t)p.w) % eb) return TL_ERR_UNSUPPORTED;
   const unsigned g = tl_grid(p.n_out, 256);
   const size_t lds = (size_t)p.Cout * p.Cin * 4;
-#define TL_TC(CO_)                                                                     \
-  case CO_:                                                                            \
-    if (dtype == TL_BF16) k_conv_tinycout<true, CO_><<<g, 256, lds, s>>>(p);           \
-    else k_conv_tinycout<false, CO_><<<g, 256, lds, s>>>(p);                           \
-    break;
+#define TL_TC(CO_)                                                                                                         \
+  case CO_:                                                                                                                \
+    return dtype == TL_BF16 ? tl_launch<k_conv_tinycout<true, CO_>>(g, 256, lds, s, p) : tl_launch<k_conv_tinycout<false, CO_>>(g, 256, lds, s, p);
   switch (p.Cout) { TL_TC(1) TL_TC(2) TL_TC(3) TL_TC(4) TL_TC(5) TL_TC(6) TL_TC(7) TL_TC(8) }
 #undef TL_TC
-  return hipGetLastError() == hipSuccess ? TL_OK : TL_ERR_LAUNCH;
+  return TL_ERR_UNSUPPORTED;                      // (not reached: 1 <= Cout <= 8 above)
 }
 
 // partial tile sets (of Cout * Cin floats) the kernel writes for n rows

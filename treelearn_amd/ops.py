@@ -70,20 +70,11 @@ def _check_table(table, K, n_out, device):
         raise ValueError(f"rulebook must be a contiguous int32 [{K}, {n_out}] tensor on {device}, got {table.dtype} {tuple(table.shape)} on {table.device}")
 
 
-def conv_fwd(x: torch.Tensor, w_packed: torch.Tensor, table, n_out: int, out: torch.Tensor = None,
-             in_scale=None, in_shift=None, in_relu=False, residual=None, out_scale=None, out_shift=None, out_relu=False,
-             out2=None, out3=None, one_hot=False, epi=None, all_ones=False, split=None, scatter=None):
-    """out[o] = epi(sum_k W[k] . pro(x[table[k][o]])); x / out / residual may be column views of wider
-    row-major buffers (their stride(0) is the leading dimension) -- that is how the skip concat is fused.
-
-    `epi` (training): "stats" -> the kernel also sums y and y^2 per channel (the statistics of the BatchNorm that consumes the result);
-    ("bn_bwd", x_bn, st, relu) -> this is the input-gradient conv of a layer fed by relu?(bn(x_bn)): the result is masked by the ReLU
-    and the sums of g and g * xhat are formed (tl_conv_args.epi_mode).  Returns (out, parts f64[.,2,Cout], nparts), or None when the
-    kernel family that serves the shape has no such epilogue (nothing was launched: the caller runs the separate passes).
-
-    `table` may be a geometry.BlockedRulebook (K = 27): x / out / residual are then in the block-local row order.  `split` = (part, Cin of
-    the logical conv) marks a launch as one input-channel half of a wider conv (bench.py's per-launch accounting).  `scatter` (with one_hot):
-    the table's scatter form i32[K][n_in] (tl_conv_args.table_scatter) -- the inverse conv then walks its input rows."""
+def _conv_args(x: torch.Tensor, w_packed: torch.Tensor, table, n_out: int, out: torch.Tensor = None,
+               in_scale=None, in_shift=None, in_relu=False, residual=None, out_scale=None, out_shift=None, out_relu=False,
+               out2=None, out3=None, one_hot=False, epi=None, all_ones=False, split=None, scatter=None):
+    """The tl_conv_args of a conv_fwd call (checked as conv_fwd documents) -> (args, out, parts, nparts, blk); parts / nparts are None
+    without `epi`.  The tensors the struct points into are the caller's and the returned ones: keep those alive while `args` is used."""
     L = _hip.lib()
     K, Cout, Cin = w_packed.shape
     if x.stride(1) != 1 or x.shape[1] != Cin:
@@ -101,8 +92,6 @@ def conv_fwd(x: torch.Tensor, w_packed: torch.Tensor, table, n_out: int, out: to
     blk = table if isinstance(table, BlockedRulebook) else None
     if blk is not None:                          # rows in block-local order: units / halo lists / local rulebooks instead of the table
         table = blk.nn_table                     # (the plain table in the new order, if the geometry carries one: shapes the staged-unit kernel does not serve)
-        global BLK_LAUNCHES
-        BLK_LAUNCHES += 1
         if x.shape[0] != n_out:
             raise ValueError("a block-local SubM conv maps the level onto itself")
         a.blk_unit = blk.unit.data_ptr(); a.blk_counter = blk.counter.data_ptr(); a.blk_halo = blk.halo.data_ptr()
@@ -143,6 +132,7 @@ def conv_fwd(x: torch.Tensor, w_packed: torch.Tensor, table, n_out: int, out: to
         setattr(a, name + "_scale", sc.data_ptr() if sc is not None else None)
         setattr(a, name + "_shift", sh.data_ptr() if sh is not None else None)
         setattr(a, name + "_relu", int(bool(relu)))
+    parts = nparts = None
     if epi is not None:
         parts = torch.empty((int(L.tl_conv_red_parts(n_out)), 2, Cout), dtype=torch.float64, device=x.device)
         nparts = ctypes.c_int32(0)
@@ -157,6 +147,43 @@ def conv_fwd(x: torch.Tensor, w_packed: torch.Tensor, table, n_out: int, out: to
             a.bn_x = xb.data_ptr(); a.bn_x_ld = xb.stride(0)
             a.bn_mean = st[0].data_ptr(); a.bn_rstd = st[1].data_ptr(); a.bn_scale = st[2].data_ptr(); a.bn_shift = st[3].data_ptr()
             a.bn_relu = int(bool(relu))
+    return a, out, parts, nparts, blk
+
+
+def conv_route(*args, **kwargs) -> str:
+    """The kernel launch(es) conv_fwd(*args, **kwargs) would make, as tl_conv_route writes them ("k_name<template args><<<grid, block,
+    lds>>>", two launches joined by " + "): the same dispatch code, nothing launched, no GPU needed (the tensors may live anywhere: only
+    their addresses and strides are looked at).  "" where conv_fwd would return None (an `epi` the shape's kernel family does not carry)."""
+    a = _conv_args(*args, **kwargs)[0]
+    buf = ctypes.create_string_buffer(1024)
+    rc = _hip.lib().tl_conv_route(ctypes.byref(a), buf, len(buf))
+    if rc != _hip.TL_ERR_UNSUPPORTED or a.epi_mode == _hip.TL_EPI_NONE:
+        _hip.check(rc, "tl_conv_route")
+    return buf.value.decode()
+
+
+def conv_fwd(x: torch.Tensor, w_packed: torch.Tensor, table, n_out: int, out: torch.Tensor = None,
+             in_scale=None, in_shift=None, in_relu=False, residual=None, out_scale=None, out_shift=None, out_relu=False,
+             out2=None, out3=None, one_hot=False, epi=None, all_ones=False, split=None, scatter=None):
+    """out[o] = epi(sum_k W[k] . pro(x[table[k][o]])); x / out / residual may be column views of wider
+    row-major buffers (their stride(0) is the leading dimension) -- that is how the skip concat is fused.
+
+    `epi` (training): "stats" -> the kernel also sums y and y^2 per channel (the statistics of the BatchNorm that consumes the result);
+    ("bn_bwd", x_bn, st, relu) -> this is the input-gradient conv of a layer fed by relu?(bn(x_bn)): the result is masked by the ReLU
+    and the sums of g and g * xhat are formed (tl_conv_args.epi_mode).  Returns (out, parts f64[.,2,Cout], nparts), or None when the
+    kernel family that serves the shape has no such epilogue (nothing was launched: the caller runs the separate passes).
+
+    `table` may be a geometry.BlockedRulebook (K = 27): x / out / residual are then in the block-local row order.  `split` = (part, Cin of
+    the logical conv) marks a launch as one input-channel half of a wider conv (bench.py's per-launch accounting).  `scatter` (with one_hot):
+    the table's scatter form i32[K][n_in] (tl_conv_args.table_scatter) -- the inverse conv then walks its input rows."""
+    L = _hip.lib()
+    a, out, parts, nparts, blk = _conv_args(x, w_packed, table, n_out, out, in_scale, in_shift, in_relu, residual, out_scale, out_shift, out_relu,
+                                            out2, out3, one_hot, epi, all_ones, split, scatter)
+    K, Cout, Cin = w_packed.shape
+    if blk is not None:
+        global BLK_LAUNCHES
+        BLK_LAUNCHES += 1
+    if epi is not None:
         rc = L.tl_conv_fwd(ctypes.byref(a), _hip.stream())
         if rc == _hip.TL_ERR_UNSUPPORTED:
             return None
