@@ -740,6 +740,47 @@ int tl_stem_keys(const double* sorted_xyz, const int64_t* sorted_label, int64_t 
 int tl_stem_profile(const double* stem_xyz, int64_t n, const int64_t* slab_start, const double* tree, int64_t n_trees, int64_t S,
                     const tl_stem_params* params, double* profile, int64_t* pcount, double* summary, int64_t* slices, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ crown structure of a labelled cloud (csrc/tl_crown.hip)
+ * Where the crown of every tree begins, how many voxels it fills, the cells it projects onto the ground and its radius in eight
+ * directions, on a grid of cell x cell x layer.  The semantics are the project's own and have no reference call site:
+ * tests/crown_restatement.py restates them in numpy float64.  All arithmetic is f64 in plain operators, no fma contraction; every other
+ * quantity is an integer count.  The rows and `tree` f64[n_trees, 4] = px, py, z_ref, z_top are those of the stem profiles above.
+ * H = z_top - z_ref; L_t = min(floor(H / layer) + 1, max_layers), 0 unless H >= 0 (NaN: none).  A row is in layer l = floor((z - z_ref) /
+ * layer) when 0 <= l < L_t, in cell (ix, iy) = (floor(x / cell), floor(y / cell)).
+ * tl_crown_voxel_keys: keys i64[n] = (t << 34) | (ix_rel << 21) | (iy_rel << 8) | l for a row of tree t = label - 1 in layer l, ix_rel =
+ *   ix - floor(px / cell) + 4096, the same in y; else the sentinel 2^55: a label outside 1 .. n_trees or a row in no layer.  *err
+ *   (device) = 1 when a row of a label in 1 .. n_trees has a coordinate that is not finite, or a row in a layer has ix_rel or iy_rel
+ *   outside 0 .. 8191 (the row gets the sentinel and the caller raises), else 0.  Every range is tested on the f64 value.
+ *   The caller sorts the keys and takes kstart i64[n_trees + 1]: kstart[t] = the first key >= t << 34.
+ * tl_crown_structure: one workgroup per tree over sorted_keys[kstart[t] .. kstart[t + 1]).  n[l] = its keys of layer l, cells[l] = the
+ *   distinct ones.  l_min = the smallest l with l * layer >= min_height (counted up from 0, at most max_layers).  With l_min < L_t and a
+ *   row in a layer >= l_min: cells_max = max cells[l] over l_min <= l < L_t, l_w the lowest l that reaches it; l_b = l_w, gap = 0, then for
+ *   l = l_w - 1 down to l_min: cells[l] * 100 >= base_percent * cells_max: l_b = l, gap = 0; else gap += 1 and stop at gap > max_gap.
+ *   A projection cell is an (ix, iy) with a key in a layer >= l_b; with c = their number, (sx, sy) = the integer sums of ix, iy over them:
+ *   u = (ix + 0.5) * cell - px, v likewise, w = u*u + v*v; sector 0 .. 7 of (u, v) counter-clockwise from +x by comparisons (u > 0, v >= 0:
+ *   v < u ? 0 : 1; u <= 0, v > 0: -u < v ? 2 : 3; u < 0, v <= 0: -v < -u ? 4 : 5; u >= 0, v < 0: u < -v ? 6 : 7; u = v = 0: 0).
+ *   counts i64[n_trees, 3] = crown_layers (L_t), crown_voxels (sum of cells[l], l >= l_b), crown_proj_cells (c);
+ *   summary f64[n_trees, 11] = crown_base_h (l_b * layer), crown_length (H - base), crown_ratio (length / H), crown_widest_h ((l_w + 0.5) *
+ *   layer), crown_volume (voxels * ((cell * cell) * layer)), crown_proj_area (c * (cell * cell)), crown_x, crown_y (((sx / c) + 0.5) *
+ *   cell), crown_offset (sqrt(dx*dx + dy*dy), dx = crown_x - px), crown_radius_max, crown_radius_mean (the sum of the eight in sector
+ *   order / 8.0); radii f64[n_trees, 8] = sqrt(max w) per sector, 0.0 for an empty one.  A tree without a crown: NaN in summary and
+ *   radii, 0 in voxels and cells.  prof_h f64[n_trees, L] = l * layer, pcount i64[n_trees, L, 2] = n[l], cells[l] for l < L_t, else NaN,
+ *   0, 0; L >= every L_t is the caller's (layers beyond L are not written).  Fewer than 2^32 rows per tree and layer.
+ *   Counts are integer adds in LDS, the sums integers, the maxima exact: the same bits run to run and for any row order.
+ * A null or misaligned pointer, a negative size, n_trees >= 2^21, L > max_layers or a parameter outside its constraint (layer, cell > 0,
+ * min_height >= 0, all finite; max_layers in 1 .. 256; base_percent in 1 .. 100; max_gap >= 0): TL_ERR_ARG, nothing launched.  Then
+ * n = 0 or n_trees = 0 (tl_crown_voxel_keys) and n_trees = 0 or L = 0 (tl_crown_structure): TL_OK without a launch, outputs and *err
+ * untouched. */
+typedef struct tl_crown_params {
+  double layer, cell, min_height;
+  int64_t max_layers, base_percent, max_gap;
+} tl_crown_params;
+int tl_crown_voxel_keys(const double* sorted_xyz, const int64_t* sorted_label, int64_t n, const double* tree, int64_t n_trees,
+                        const tl_crown_params* params, int64_t* keys, int32_t* err, tl_stream_t stream);
+int tl_crown_structure(const int64_t* sorted_keys, int64_t n, const int64_t* kstart, const double* tree, int64_t n_trees, int64_t L,
+                       const tl_crown_params* params, double* summary, int64_t* counts, double* prof_h, int64_t* pcount, double* radii,
+                       tl_stream_t stream);
+
 /* ------------------------------------------------------------------ LAS point records (csrc/tl_las.hip)
  * The record passes of the LAS reader and writer (treelearn_amd/util/las.py parses and writes the headers on the host).  The layout is
  * the ASPRS one and the rules are restated in numpy in tests/las_restatement.py; all arithmetic is f64 in plain operators, no fma

@@ -101,6 +101,10 @@ class StemParams(_c.Structure):            # tl_stem_params
                [(k, _i64) for k in ("max_slices", "min_points", "max_misses")]
 
 
+class CrownParams(_c.Structure):           # tl_crown_params
+    _fields_ = [(k, _c.c_double) for k in ("layer", "cell", "min_height")] + [(k, _i64) for k in ("max_layers", "base_percent", "max_gap")]
+
+
 _I4 = _i32 * 4
 _I3 = _i32 * 3
 
@@ -193,6 +197,8 @@ PROTOTYPES = {
     "tl_tree_ground": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _c.c_double, _c.c_double, _c.c_double, _i64, _vp, _vp, _vp]),
     "tl_stem_keys": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _c.POINTER(StemParams), _vp, _vp]),
     "tl_stem_profile": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _c.POINTER(StemParams), _vp, _vp, _vp, _vp, _vp]),
+    "tl_crown_voxel_keys": (_i32, [_vp, _vp, _i64, _vp, _i64, _c.POINTER(CrownParams), _vp, _vp, _vp]),
+    "tl_crown_structure": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _c.POINTER(CrownParams), _vp, _vp, _vp, _vp, _vp, _vp]),
     "tl_las_decode": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _c.c_double * 3, _c.c_double * 3, _vp, _i32, _i64, _i32, _vp]),
     "tl_las_encode": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _i64, _c.c_double * 3, _c.c_double * 3, _vp, _i64, _vp, _vp, _vp, _vp]),
     "tl_pointwise_eval_ws_bytes": (_i64, [_i64]),

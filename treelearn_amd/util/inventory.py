@@ -28,7 +28,10 @@ height_ag = z_top - z_ground, base_gap = z_low - z_ground, and dbh_ag, dbh_ag_x,
 z_ground in place of z_low (tl_tree_ground).  NaN, and dbh_ag_n = 0, where the terrain has no value under the tree.
 
 With stem=True (util.stem) the seven STEM_COLUMNS follow them, and the key "stem_profile" holds the circle of every slab
-along every stem: the stage runs on the same label-sorted rows and tree table, heights from z_ground with a terrain, else from z_low."""
+along every stem: the stage runs on the same label-sorted rows and tree table, heights from z_ground with a terrain, else from z_low.
+
+With crown=True (util.crown) the fourteen CROWN_COLUMNS follow them, and the key "crown_profile" holds the rows and cells of
+every layer of every tree and its crown radii in eight sectors: the same rows, table and reference height."""
 import argparse
 import csv
 import sys
@@ -105,7 +108,7 @@ def _device_inputs(coords, labels):
 
 
 def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh_max_radius=1.0, dbh_min_points=8, crown_cell=0.25,
-                   offset=None, stages=None, terrain=None, stem=False, stem_cfg=None):
+                   offset=None, stages=None, terrain=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None):
     """coords [N, 3] float32 or float64 (a row stride of 3 or 4 elements is read in place), labels [N] integers; numpy arrays or tensors,
     on the host or the device.  Returns a dict of numpy arrays of length T = max(label), keyed by COLUMNS (tree_id = 1..T).
     `offset` (3 values) is added to x, y, z, z_low, z_top, dbh_x, dbh_y at the end -- the un-centring of segment_forest.
@@ -113,7 +116,12 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     `terrain`: a util.terrain.Terrain in the frame of `coords`; the dict then holds GROUND_COLUMNS after COLUMNS (`offset` is added to
     z_ground, dbh_ag_x, dbh_ag_y as well).
     `stem`: True adds util.stem's STEM_COLUMNS after them and "stem_profile", a dict of [T, S] arrays (h, x, y, r, rmse, n, state;
-    `offset` is added to its x, y); stem_cfg holds any of util.stem's parameters."""
+    `offset` is added to its x, y); stem_cfg holds any of util.stem's parameters.
+    `crown`: True adds util.crown's CROWN_COLUMNS after them and "crown_profile", a dict of [T, L] arrays (h, n, cells) and radii [T, 8]
+    (`offset` is added to crown_x, crown_y); crown_cfg holds any of util.crown's parameters."""
+    if crown:
+        from . import crown as _crown
+        crown_cfg = _crown.check_params(crown_cfg)                                    # before any GPU work
     if stem:
         from . import stem as _stem
         stem_cfg = _stem.check_params(stem_cfg)                                       # before any GPU work
@@ -178,20 +186,28 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
         _hip.check(L.tl_crown_count(_hip.ptr(keys), m, T, _hip.ptr(cells), _hip.stream()), "tl_crown_count")
     mark("crown keys + count")
 
-    if stem:
+    if stem or crown:
         z_ref = gtable[:, 0] if terrain is not None else table[:, 0]
         tree = torch.stack([table[:, 3], table[:, 4], z_ref, table[:, 1]], 1).contiguous()
+    if stem:
         stem_dev = _stem.stem_stage(xyz, kept_lab, T, tree, stem_cfg, mark)
+    if crown:
+        *crown_dev, crown_err = _crown.crown_stage(xyz, kept_lab, T, tree, crown_cfg, mark)
 
     table_h, counts_h, cells_h = table.cpu().numpy(), counts.cpu().numpy(), cells.cpu().numpy()
     if terrain is not None:
         gtable_h, gcount_h = gtable.cpu().numpy(), gcount.cpu().numpy()
     if stem:
         stem_out = _stem.to_columns(*(t.cpu().numpy() for t in stem_dev), off)
+    if crown:
+        crown_out = _crown.to_columns(*(t.cpu().numpy() for t in crown_dev), off)
+        crown_bad = crown_err is not None and int(crown_err.item())
     bad = err is not None and int(err.item())
     mark("D2H")
     if bad:
         raise ValueError(f"a coordinate is not finite or lies beyond 2^20 crown cells of {p['crown_cell']} m from the origin: centre the cloud")
+    if crown and crown_bad:
+        raise _crown.crown_error(crown_cfg)
 
     out = {k: np.ascontiguousarray(table_h[:, j]) for j, k in enumerate(_TABLE)}
     out["tree_id"] = np.arange(1, T + 1, dtype=np.int64)
@@ -208,6 +224,9 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     if stem:
         out.update(stem_out)
         stem_keys = _stem.STEM_COLUMNS + ("stem_profile",)
+    if crown:
+        out.update(crown_out)
+        stem_keys = stem_keys + _crown.CROWN_COLUMNS + ("crown_profile",)
     if terrain is None:
         return {k: out[k] for k in COLUMNS + stem_keys}
     out.update({k: np.ascontiguousarray(gtable_h[:, j]) for j, k in enumerate(_GROUND_TABLE)})
@@ -218,11 +237,12 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     return {k: out[k] for k in COLUMNS + GROUND_COLUMNS + stem_keys}
 
 
-def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None, **params):
+def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None, **params):
     """The inventory of an N x 4 cloud (x y z label), as the command line computes it: the coordinates are centred on their float64 mean
     on the device, as segment_forest centres its input, and the mean is handed back as `offset`.  terrain=True builds the terrain of
     the label-0 rows in the same frame (util.terrain.terrain_model, parameters in terrain_cfg) and adds the GROUND_COLUMNS; stem=True
-    adds util.stem's STEM_COLUMNS and "stem_profile" (parameters in stem_cfg)."""
+    adds util.stem's STEM_COLUMNS and "stem_profile" (parameters in stem_cfg); crown=True adds util.crown's CROWN_COLUMNS and
+    "crown_profile" (parameters in crown_cfg)."""
     import torch
     pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points))
     if pts.ndim != 2 or pts.shape[1] != 4:
@@ -234,26 +254,33 @@ def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cf
     if stem:
         from .stem import check_params as check_stem
         stem_cfg = check_stem(stem_cfg)
+    if crown:
+        from .crown import check_params as check_crown
+        crown_cfg = check_crown(crown_cfg)
     if not torch.cuda.is_available():
         raise RuntimeError("treelearn_amd.util.inventory runs on the GPU (tl_tree_inventory); there is no CPU fallback")
     pts = pts.to("cuda")
     xyz, lab = pts[:, :3].to(torch.float64), pts[:, 3].to(torch.int64)
     if len(xyz) == 0:
-        return tree_inventory(xyz, lab, terrain=terrain_model(xyz, lab, **terrain_cfg) if terrain else None, stem=stem, stem_cfg=stem_cfg, **params)
+        return tree_inventory(xyz, lab, terrain=terrain_model(xyz, lab, **terrain_cfg) if terrain else None, stem=stem, stem_cfg=stem_cfg, crown=crown,
+                              crown_cfg=crown_cfg, **params)
     mean = xyz.mean(0)
     centred = xyz - mean
     return tree_inventory(centred, lab, offset=mean, terrain=terrain_model(centred, lab, **terrain_cfg) if terrain else None, stem=stem,
-                          stem_cfg=stem_cfg, **params)
+                          stem_cfg=stem_cfg, crown=crown, crown_cfg=crown_cfg, **params)
 
 
 def write_inventory(path, inv, categories=None):
     """CSV: a header row, then one row per tree; floats as repr (they read back to the same bits), NaN as `nan`.  `categories` (per tree:
     index into segment.CATEGORIES) adds a `category` column of names.  The columns are those the dict holds: COLUMNS, and GROUND_COLUMNS
-    after them when the inventory was taken with a terrain, then util.stem's STEM_COLUMNS when it was taken with stem=True."""
+    after them when the inventory was taken with a terrain, then util.stem's STEM_COLUMNS when it was taken with stem=True, then
+    util.crown's CROWN_COLUMNS when it was taken with crown=True (each group only when the dict holds all of it)."""
+    from .crown import CROWN_COLUMNS, CROWN_INT_COLUMNS
     from .stem import STEM_COLUMNS
     T = len(inv["tree_id"])
-    columns = COLUMNS + (GROUND_COLUMNS if all(k in inv for k in GROUND_COLUMNS) else ()) + (STEM_COLUMNS if all(k in inv for k in STEM_COLUMNS) else ())
-    ints = INT_COLUMNS + ("dbh_ag_n", "stem_slices")
+    columns = COLUMNS + (GROUND_COLUMNS if all(k in inv for k in GROUND_COLUMNS) else ()) + (STEM_COLUMNS if all(k in inv for k in STEM_COLUMNS) else ()) + \
+        (CROWN_COLUMNS if all(k in inv for k in CROWN_COLUMNS) else ())
+    ints = INT_COLUMNS + ("dbh_ag_n", "stem_slices") + CROWN_INT_COLUMNS
     names = None
     if categories is not None:
         from .segment import CATEGORIES
@@ -295,11 +322,15 @@ def main(argv=None):
     ap.add_argument("--stem", action="store_true", help="add the stem columns: slices, base and top height, volume, DBH, lean and taper of the stem profile")
     from . import stem as _stem
     _stem.add_arguments(ap)
+    ap.add_argument("--crown", action="store_true", help="add the crown columns: crown base, length, ratio, volume, projection area, centroid and radii")
+    from . import crown as _crown
+    _crown.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         params = check_params(params_of(a))
         terrain_cfg = _terrain.check_params(_terrain.params_of(a))
         stem_cfg = _stem.check_params(_stem.params_of(a))
+        crown_cfg = _crown.check_params(_crown.params_of(a))
     except ValueError as e:
         ap.error(str(e))
     if not os.path.exists(a.forest):
@@ -309,7 +340,7 @@ def main(argv=None):
     if data.shape[1] != 4:
         ap.error(f"--forest {a.forest}: expected N x 4 (x y z label), got {data.shape}")
     inv = cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, stem=a.stem, stem_cfg=stem_cfg if a.stem else None,
-                          **params)
+                          crown=a.crown, crown_cfg=crown_cfg if a.crown else None, **params)
     write_inventory(a.out, inv)
     ok = int(np.isfinite(inv["dbh"]).sum())
     print(f"{a.forest}: {len(data)} points, {len(inv['tree_id'])} trees, {ok} with a DBH -> {a.out}")

@@ -158,7 +158,8 @@ def segment_from_pointwise(coords, offset_predictions, instance_preds, shape_cfg
 
 
 def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=None, return_type="original", logger=None,
-                   return_pointwise=False, inventory=False, inventory_cfg=None, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None):
+                   return_pointwise=False, inventory=False, inventory_cfg=None, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None,
+                   crown=False, crown_cfg=None):
     """points: N x 3 or N x 4 (x y z [label]) f64, host or device.  Returns numpy arrays: coords (f64, input frame), labels (i64),
     categories (per tree 1..T, index into CATEGORIES), and with return_pointwise the arrays of pipeline.py:100-111 (ensembled rows).
     inventory=True adds result["inventory"]: util.inventory.tree_inventory of the returned coords / labels, computed on the device in
@@ -167,7 +168,13 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
     centred frame; the un-centred Terrain.to_host()) and result["height_above_ground"] (f64 [N], row-aligned with coords); terrain_cfg
     holds any of its five parameters.  With inventory=True as well, the inventory gets the ground columns.
     stem=True implies inventory=True and adds util.stem's columns and result["inventory"]["stem_profile"] (the circle of every slab along
-    every stem); stem_cfg holds any of util.stem's parameters."""
+    every stem); stem_cfg holds any of util.stem's parameters.
+    crown=True implies inventory=True and adds util.crown's columns and result["inventory"]["crown_profile"] (rows and cells per layer,
+    crown radii per sector); crown_cfg holds any of util.crown's parameters."""
+    if crown:
+        from .crown import check_params as check_crown
+        crown_cfg = check_crown(crown_cfg)                                            # before any GPU work
+        inventory = True
     if stem:
         from .stem import check_params as check_stem
         stem_cfg = check_stem(stem_cfg)                                               # before any GPU work
@@ -226,7 +233,7 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
     if inventory:
         _log(logger, "computing the tree inventory")
         result["inventory"] = tree_inventory(r["coords"], r["labels"], offset=mean, terrain=dtm, stem=stem, stem_cfg=stem_cfg if stem else None,
-                                             **inventory_cfg)
+                                             crown=crown, crown_cfg=crown_cfg if crown else None, **inventory_cfg)
     if return_pointwise:
         pw = dict(coords=coords, offset_predictions=off, offset_labels=offl, semantic_prediction_logits=sem, semantic_labels=seml,
                   instance_labels=instl, backbone_feats=bb, input_feats=infeat, instance_preds=inst, instance_preds_after_initial_clustering=initial)
@@ -286,7 +293,7 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
     pointwise_results/pointwise_results.npz + cluster_coords_initial / cluster_coords (first format) when the result holds them;
     tree_inventory.csv (util.inventory.write_inventory, with the category names) when the result holds an inventory; terrain.npz
     (util.terrain.write_terrain) and height_above_ground.npy when it holds a terrain; stem_profiles.npz (util.stem.write_stem_profiles) when
-    the inventory holds stem profiles."""
+    the inventory holds stem profiles; crown_profiles.npz (util.crown.write_crown_profiles) when it holds crown profiles."""
     save_formats = list(save_formats)
     check_formats(save_formats)
     coords, labels = np.asarray(result["coords"], np.float64), np.asarray(result["labels"], np.int64)
@@ -333,6 +340,9 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
         if "stem_profile" in result["inventory"]:
             from .stem import write_stem_profiles
             write_stem_profiles(os.path.join(out_dir, "stem_profiles.npz"), result["inventory"])
+        if "crown_profile" in result["inventory"]:
+            from .crown import write_crown_profiles
+            write_crown_profiles(os.path.join(out_dir, "crown_profiles.npz"), result["inventory"])
     if "terrain" in result:
         from .terrain import write_terrain
         os.makedirs(out_dir, exist_ok=True)
@@ -404,11 +414,15 @@ def parse_args(argv=None):
     ap.add_argument("--stem", action="store_true", help="write stem_profiles.npz and add the stem columns to tree_inventory.csv (implies --inventory)")
     from . import stem as _stem
     _stem.add_arguments(ap)
+    ap.add_argument("--crown", action="store_true", help="write crown_profiles.npz and add the crown columns to tree_inventory.csv (implies --inventory)")
+    from . import crown as _crown
+    _crown.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         check_params(params_of(a))
         _terrain.check_params(_terrain.params_of(a))
         _stem.check_params(_stem.params_of(a))
+        _crown.check_params(_crown.params_of(a))
     except ValueError as e:
         ap.error(str(e))
     check_formats(a.formats)
@@ -449,12 +463,13 @@ def main(argv=None):
                     tau_vert=a.tau_vert, tau_off=a.tau_off)
     shape = dict(SHAPE_CFG, alpha=a.alpha, buffer_size_to_determine_edge_trees=a.edge_buffer, outer_remove=a.outer_remove)
     with torch.no_grad():
-        from . import stem as _stem, terrain as _terrain
+        from . import crown as _crown, stem as _stem, terrain as _terrain
         from .inventory import params_of
         res = segment_forest(points, model, sample, grouping, shape, a.return_type, logger, return_pointwise=a.save_pointwise,
-                             inventory=a.inventory, inventory_cfg=params_of(a) if a.inventory or a.stem else None,
+                             inventory=a.inventory, inventory_cfg=params_of(a) if a.inventory or a.stem or a.crown else None,
                              terrain=a.terrain, terrain_cfg=_terrain.params_of(a) if a.terrain else None,
-                             stem=a.stem, stem_cfg=_stem.params_of(a) if a.stem else None)
+                             stem=a.stem, stem_cfg=_stem.params_of(a) if a.stem else None,
+                             crown=a.crown, crown_cfg=_crown.params_of(a) if a.crown else None)
     plot_name = os.path.splitext(os.path.basename(a.forest))[0]
     save_results(res, a.out, plot_name, a.formats, save_treewise=not a.no_treewise, save_pointwise=a.save_pointwise)
     cats = np.bincount(res["categories"], minlength=3)
