@@ -473,6 +473,33 @@ int tl_group_mean(const float* src, int64_t n, int C, const int64_t* sorted_keys
 int tl_verticality(const double* xyz_sorted, const int64_t* sorted_keys, int64_t n, double radius, const int64_t* extent2,
                    float* out, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ geometric point features
+ * Replaces jakteristics.compute_features(points, search_radius, feature_names=[...]) for ANY list of its feature
+ * names (data_preparation.py:82-88, "verticality (and optionally other features)").  jakteristics is not part of
+ * the reference tree: the definitions are restated (parity unpinned, as for tl_verticality).
+ *
+ * tl_eigen_features: xyz_sorted f64[n,3], sorted_keys and extent2 as for tl_verticality (tl_cell_keys with a
+ *   `radius`-sized cell, round_input = 0, sorted with z fastest).  piece_start i64[n_pieces] device: the work table,
+ *   ascending or not: the sorted index of every point that starts an (x, y) column of cells (key >> 21 differs from
+ *   its predecessor's) or whose index is a multiple of 64; one wave serves one piece, the points from there to the
+ *   next such index.  A point whose piece is missing from the table is not written.  cols = HOST i32[F] feature ids,
+ *   1 <= F <= TL_FEAT_COUNT;
+ *   out f32[n,F] in sorted order.  Neighbourhood: squared distance <= radius^2, the point itself included; sums of
+ *   d and d d^T relative to the query point in f64, added in the order of the sorted array; sample covariance
+ *   (n - 1); all eigenpairs by cyclic Jacobi in f64 with l1 >= l2 >= l3 clamped at 0 and every eigenvector oriented
+ *   by z >= 0 (z == 0: y >= 0; that 0 too: x >= 0).  Fewer than 3 neighbours: NaN in every column except
+ *   number_of_neighbors; a ratio with a zero denominator is NaN.  Ids, with s = l1 + l2 + l3:
+ *    0 eigenvalue_sum s          1 omnivariance cbrt(l1 l2 l3)   2 eigenentropy -sum l ln l (0 ln 0 = 0)
+ *    3 anisotropy (l1-l3)/l1     4 planarity (l2-l3)/l1          5 linearity (l1-l2)/l1
+ *    6 PCA1 l1/s                 7 PCA2 l2/s                     8 surface_variation l3/s
+ *    9 sphericity l3/l1         10 verticality 1-|e3z|          11..13 nx ny nz = e3
+ *   14 number_of_neighbors      15..17 eigenvalue1..3           18..26 eigenvector1x .. eigenvector3z
+ *   Compiled without contraction: the same bits on every run, whatever the piece table's order.  One launch, no
+ *   atomics.  TL_ERR_ARG on a null pointer, n or n_pieces <= 0, n_pieces > n, F or an id out of range. */
+enum { TL_FEAT_COUNT = 27 };
+int tl_eigen_features(const double* xyz_sorted, const int64_t* sorted_keys, int64_t n, double radius, const int64_t* extent2,
+                      const int64_t* piece_start, int64_t n_pieces, const int32_t* cols, int F, float* out, tl_stream_t stream);
+
 /* ------------------------------------------------------------------ random training crops
  * The random-crop half of SampleGenerator (tree_learn/util/data_preparation.py:136-330) on a plot resident in HBM; the
  * grid and candidate lay-out stay on the host (util/crops.py).  f64 wherever the reference is f64, no fma contraction.

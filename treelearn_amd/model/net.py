@@ -35,6 +35,7 @@ class TreeLearn(nn.Module):
         self.fixed_modules = fixed_modules
         self.use_feats = use_feats
         self.use_coords = use_coords
+        self.dim_coord, self.dim_feat = dim_coord, dim_feat
         self.spatial_shape = spatial_shape
         self.max_num_points_per_voxel = max_num_points_per_voxel
         self.num_blocks = num_blocks

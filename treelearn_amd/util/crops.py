@@ -32,7 +32,7 @@ f32, f64 = np.float32, np.float64
 # configs/data_gen/gen_train_data.yaml + configs/_modular/sample_generation.yaml of the reference (ints stay ints: they reach the json files)
 TRAIN_CFG = dict(occupancy_res=1, n_points_to_calculate_occupancy=100000, min_percent_occupied_fill=0.9, how_far_fill=9,
                  min_percent_occupied_choose=0.45, n_samples_total=25000, chunk_size=35, voxel_size=0.1, search_radius_features=0.6,
-                 n_neigh_sor=None, multiplier_sor=None, rad=None, npoints_rad=None)
+                 n_neigh_sor=None, multiplier_sor=None, rad=None, npoints_rad=None, feature_names=["verticality"])
 _FILTER_KEYS = ("n_neigh_sor", "multiplier_sor", "rad", "npoints_rad")
 
 
@@ -256,10 +256,11 @@ def _meta(plot_name, rotation_angle, cfg):
             "multiplier_sor": cfg["multiplier_sor"], "rad": cfg["rad"], "npoints_rad": cfg["npoints_rad"]}
 
 
-def _load_plot(path_vox, path_feat):
+def _load_plot(path_vox, path_feat, feature_names=("verticality",)):
+    from .features import load_feature_cache
     d = np.load(path_vox)
     data = np.hstack((d["points"], d["labels"][:, np.newaxis]))                   # data_preparation.py:113-119
-    feats = np.load(path_feat)["features"]
+    feats = load_feature_cache(path_feat, feature_names)                          # ValueError: a cache written for another list
     return data[:, :3], data[:, 3], feats
 
 
@@ -276,10 +277,12 @@ def generate_random_crops(base_dir, cfg=None, seed=0, logger=None):
 
     Plots are processed in file-name order; the reference uses os.listdir order, which the file system decides.
     Returns {plot: number of crops written}."""
+    from .features import check_feature_names, save_feature_cache
     from .prepare import compute_features, voxelize
     from .segment import load_forest
     cfg = dict(TRAIN_CFG, **(cfg or {}))
     filters = check_cfg(cfg)
+    names = check_feature_names(cfg["feature_names"], for_model=True)             # before anything is written
     rs = np.random.RandomState(seed)
     say = (lambda m: logger.info(m)) if logger is not None else (lambda m: None)
     forests_dir = osp.join(base_dir, "forests")
@@ -309,8 +312,8 @@ def generate_random_crops(base_dir, cfg=None, seed=0, logger=None):
         if osp.exists(save_path):
             continue
         d = np.load(osp.join(voxelized_dir, plot_file))
-        feats = compute_features(d["points"].astype(np.float64), search_radius=cfg["search_radius_features"])
-        np.savez_compressed(save_path, features=feats.cpu().numpy())
+        feats = compute_features(d["points"].astype(np.float64), search_radius=cfg["search_radius_features"], feature_names=names)
+        save_feature_cache(save_path, feats.cpu().numpy(), names)
 
     say("calculating occupancy...")
     grids, n_occupied = {}, {}
@@ -319,7 +322,7 @@ def generate_random_crops(base_dir, cfg=None, seed=0, logger=None):
         if osp.exists(occupancy_path):
             grid = np.load(occupancy_path)["occupancy_grid"]
         else:
-            points, labels, _ = _load_plot(osp.join(voxelized_dir, plot_file), osp.join(features_dir, plot_file))
+            points, labels, _ = _load_plot(osp.join(voxelized_dir, plot_file), osp.join(features_dir, plot_file), names)
             grid = occupancy_grid(points, labels, rs, cfg["occupancy_res"], cfg["n_points_to_calculate_occupancy"], cfg["how_far_fill"],
                                   cfg["min_percent_occupied_fill"])["grid"]
             np.savez_compressed(occupancy_path, occupancy_grid=grid)
@@ -331,7 +334,7 @@ def generate_random_crops(base_dir, cfg=None, seed=0, logger=None):
     written = {}
     for plot_file in plot_files:
         plot_name = osp.basename(plot_file)[:-4]
-        points, labels, feats = _load_plot(osp.join(voxelized_dir, plot_file), osp.join(features_dir, plot_file))
+        points, labels, feats = _load_plot(osp.join(voxelized_dir, plot_file), osp.join(features_dir, plot_file), names)
         n_plot = n_samples[plot_file.replace(".npz", "")]
         x_range, y_range = get_ranges(points)
         centres, angles, rinv = crop_candidates(x_range, y_range, rs, cfg["n_samples_total"], n_plot)
@@ -371,9 +374,13 @@ def parse_args(argv=None):
         ap.add_argument("--" + k.replace("_", "-"), type=_number, default=TRAIN_CFG[k])
     for k in _FILTER_KEYS:                                      # the outlier filters of util/outlier.py: off unless both keys of a pair are given
         ap.add_argument("--" + k.replace("_", "-"), type=_number, default=None)
+    ap.add_argument("--feature-names", nargs="+", default=list(TRAIN_CFG["feature_names"]),
+                    help="point features of the crops (util/features.py), at most 5, verticality last")
     a = ap.parse_args(argv)
     try:
         check_cfg({k: getattr(a, k) for k in _FILTER_KEYS})
+        from .features import check_feature_names
+        check_feature_names(a.feature_names, for_model=True)
     except (NotImplementedError, ValueError) as e:
         ap.error(str(e))
     for k in ("n_samples_total", "chunk_size", "occupancy_res", "n_points_to_calculate_occupancy", "voxel_size", "search_radius_features"):

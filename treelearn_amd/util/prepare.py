@@ -3,11 +3,11 @@
 predictions back to the original cloud (util/pipeline.py:423-452).
 
   voxelize           <- data_preparation.py:60-79 (open3d 0.17.0 VoxelDownSampleAndTrace)
-  compute_features   <- data_preparation.py:82-100 (jakteristics 0.5.1, verticality, search radius 0.6 m)
+  compute_features   <- data_preparation.py:82-100 (jakteristics 0.5.1, search radius 0.6 m: verticality, or any list of its feature names)
   propagate_to_original <- util/pipeline.py:441-452 (`propagate_preds_hash_full`: hash dictionary voxel -> original indices)
 
 open3d and jakteristics are not part of the reference tree and not installable here: their published algorithms are
-restated (csrc/tl_prepare.hip) and checked against an independent numpy/scipy oracle; parity with the two libraries
+restated (csrc/tl_prepare.hip, csrc/tl_features.hip) and checked against an independent numpy/scipy oracle; parity with the two libraries
 themselves is unpinned.  Deliberate differences, all on quantities the path does not depend on: voxels come out in
 ascending (x, y, z) order (open3d: unordered_map order), and points with fewer than three neighbours inside the search
 radius get NaN -> column mean (jakteristics diagonalises a rank-deficient covariance there)."""
@@ -73,8 +73,13 @@ def voxelize(data, voxel_size, round_first=False):
 
 
 def compute_features(points, search_radius=0.6, feature_names=("verticality",)):
-    """points [N,3] -> float32 [N,1] verticality, NaNs replaced by the mean of the finite values (replace_nanfeatures)."""
-    assert list(feature_names) == ["verticality"], "only the verticality feature is on the path (util/pipeline.py:64)"
+    """points [N,3] -> float32 [N,F] in the order of `feature_names` (any of util.features.FEATURE_NAMES, no duplicates), NaNs replaced
+    per column by the mean of the column's finite values (replace_nanfeatures).  ["verticality"] alone is the path of the pipeline
+    (util/pipeline.py:64) through tl_verticality; every other list goes through tl_eigen_features."""
+    from .features import feature_ids
+    ids = feature_ids(feature_names)                                                  # ValueError before any GPU work
+    if list(feature_names) != ["verticality"]:
+        return _eigen_features(points, search_radius, ids)
     L = _hip.lib()
     xyz = _dev_f64(points)
     n = len(xyz)
@@ -89,6 +94,53 @@ def compute_features(points, search_radius=0.6, feature_names=("verticality",)):
     if bool(nan.any()):
         out[nan] = out[~nan].double().mean().float() if bool((~nan).any()) else float("nan")
     return out.reshape(-1, 1)
+
+
+PIECE = 64                                                                             # points per wave of tl_eigen_features
+_COLUMN_SHIFT = 21                                                                     # tl_cell_keys: z-cell in the low 21 bits
+
+
+def feature_pieces(sorted_keys):
+    """The work table of tl_eigen_features (device i64[n_pieces]): the sorted index of every point that starts an (x, y) column of cells
+    or whose index is a multiple of PIECE.  Its length is the one value read back to the host."""
+    n = len(sorted_keys)
+    col = sorted_keys >> _COLUMN_SHIFT
+    start = (torch.arange(n, dtype=torch.int64, device=sorted_keys.device) % PIECE) == 0
+    start[1:] |= col[1:] != col[:-1]
+    return torch.nonzero(start).squeeze(1).contiguous()
+
+
+def sorted_cells(xyz, search_radius):
+    """f64 device points -> (points sorted by their `search_radius`-sized cell with z fastest, sorted keys, stable permutation, extent)."""
+    origin = float(xyz.min()) - search_radius
+    keys, ext = _keys(xyz, search_radius, origin, False)
+    skeys, perm = torch.sort(keys, stable=True)
+    return xyz.index_select(0, perm).contiguous(), skeys, perm, ext
+
+
+def eigen_features_sorted(sx, skeys, ext, pieces, search_radius, ids):
+    """tl_eigen_features on sorted points: f32 [n, len(ids)] in sorted order, NaNs left in."""
+    L = _hip.lib()
+    n, F = len(sx), len(ids)
+    out = torch.empty((n, F), dtype=torch.float32, device=sx.device)
+    cols = (ctypes.c_int32 * F)(*ids)
+    _hip.check(L.tl_eigen_features(_hip.ptr(sx), _hip.ptr(skeys), n, float(search_radius), _I64x2(ext[0], ext[1]), _hip.ptr(pieces), len(pieces),
+                                   ctypes.cast(cols, ctypes.c_void_p), F, _hip.ptr(out), _hip.stream()), "tl_eigen_features")
+    return out
+
+
+def _eigen_features(points, search_radius, ids, replace_nan=True):
+    """compute_features through tl_eigen_features; replace_nan=False leaves the NaNs of the definition in (what the tests compare)."""
+    xyz = _dev_f64(points)
+    sx, skeys, perm, ext = sorted_cells(xyz, search_radius)
+    v = eigen_features_sorted(sx, skeys, ext, feature_pieces(skeys), search_radius, ids)
+    out = torch.empty_like(v); out[perm] = v
+    if not replace_nan:
+        return out
+    finite = ~torch.isnan(out)
+    # per column: f64 sum of the finite values / their count, cast to f32 (a column without a finite value stays NaN)
+    mean = (torch.where(finite, out.double(), torch.zeros((), dtype=torch.float64, device=out.device)).sum(0) / finite.sum(0).double()).float()
+    return torch.where(finite, out, mean.expand_as(out)).contiguous()
 
 
 def propagate_to_original(preds_voxelized, trace):

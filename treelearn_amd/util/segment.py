@@ -30,7 +30,7 @@ SAVE_FORMATS = ("npz", "npy", "txt", "las", "laz")
 CATEGORIES = ("completely_inside", "trunk_base_inside", "trunk_base_outside")
 
 # configs/pipeline/pipeline.yaml + configs/_modular/{sample_generation,grouping,model}.yaml of the reference
-SAMPLE_CFG = dict(voxel_size=0.1, search_radius_features=0.6, inner_edge=8.0, outer_edge=13.5, stride=0.5)
+SAMPLE_CFG = dict(voxel_size=0.1, search_radius_features=0.6, inner_edge=8.0, outer_edge=13.5, stride=0.5, feature_names=["verticality"])
 GROUPING_CFG = dict(tree_conf_thresh=0.5, tau_vert=0.6, tau_off=4.0, tau_group=0.15, tau_min=50, use_hdbscan=True)
 SHAPE_CFG = dict(outer_remove=None, alpha=0.6, buffer_size_to_determine_edge_trees=0.3)
 MODEL_CFG = dict(channels=32, num_blocks=7, kernel_size=3, use_feats=False, use_coords=False, dim_coord=3, dim_feat=1,
@@ -190,6 +190,11 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
     shape_cfg = dict(SHAPE_CFG, **(shape_cfg or {})) if isinstance(shape_cfg, (dict, type(None))) else shape_cfg
     if return_type not in RETURN_TYPES:
         raise ValueError(f"return_type must be one of {RETURN_TYPES}, got {return_type!r}")
+    from .features import check_feature_names
+    feature_names = check_feature_names(_get(sample_cfg, "feature_names", None) or ["verticality"], for_model=True)
+    if bool(getattr(model, "use_feats", False)) and int(getattr(model, "dim_feat", len(feature_names))) != len(feature_names):
+        raise ValueError(f"the model was built with use_feats=True and dim_feat={model.dim_feat}, but feature_names holds "
+                         f"{len(feature_names)} features: {feature_names}")                   # before the tile loop, not the executor's TypeError inside it
     pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points))
     if pts.ndim != 2 or pts.shape[1] not in (3, 4):
         raise ValueError(f"points must be N x 3 or N x 4, got {tuple(pts.shape)}")
@@ -200,7 +205,7 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
     _log(logger, "voxelizing and computing features")
     down, trace = voxelize(centred, vs)
     vox = down[:, :3].float().contiguous()
-    feats = compute_features(vox, float(_get(sample_cfg, "search_radius_features", 0.6)))
+    feats = compute_features(vox, float(_get(sample_cfg, "search_radius_features", 0.6)), feature_names)
     tiler = PlotTiler(vox, torch.full((len(vox),), -1.0, device=vox.device), feats)
     inner = float(_get(sample_cfg, "inner_edge"))
     tiles = tiler.tiles(inner, float(_get(sample_cfg, "outer_edge")), float(_get(sample_cfg, "stride")), inner, offset_labels="none",

@@ -214,7 +214,7 @@ class PlotTiler:
 
 # ------------------------------------------------------------------------------------------------ validation tiles on disk
 # configs/data_gen/gen_val_data.yaml over configs/_modular/sample_generation.yaml of the reference (stride 1: tiles do not overlap)
-VAL_CFG = dict(voxel_size=0.1, search_radius_features=0.6, inner_edge=8, outer_edge=13.5, stride=1,
+VAL_CFG = dict(voxel_size=0.1, search_radius_features=0.6, inner_edge=8, outer_edge=13.5, stride=1, feature_names=["verticality"],
                sample_generator=dict(n_neigh_sor=None, multiplier_sor=None, rad=None, npoints_rad=None))
 _FILTER_KEYS = ("n_neigh_sor", "multiplier_sor", "rad", "npoints_rad")
 
@@ -226,9 +226,11 @@ def write_tiles(forest_path, sample_cfg=None, logger=None):
     <base>/tiles/npz/<plot>_<i>.npz (points f32 centred on the tile, feat f32, instance_label i32, center f64[3]) and
     <base>/tiles/json/<plot>_<i>.json per tile whose inner square holds a point, i counting those tiles.  `CropDataset(<base>/tiles/npz,
     inner_square_edge_length, training=False)` reads them.  Returns the number of tiles written."""
+    from .features import check_feature_names, load_feature_cache, save_feature_cache
     from .prepare import compute_features, voxelize
     from .segment import load_forest
     cfg = dict(VAL_CFG, **{k: v for k, v in dict(sample_cfg or {}).items()})
+    names = check_feature_names(cfg["feature_names"], for_model=True)         # before anything is written
     gen = dict(VAL_CFG["sample_generator"], **dict(cfg.get("sample_generator") or {}))
     from .outlier import active_filters
     filters = active_filters({k: gen.get(k) for k in _FILTER_KEYS})          # a half-set pair is refused here, before anything is written
@@ -254,12 +256,12 @@ def write_tiles(forest_path, sample_cfg=None, logger=None):
     path_feat = osp.join(features_dir, f"{plot_name}.npz")
     if not osp.exists(path_feat):
         pts = np.load(path_vox)["points"]
-        feats = compute_features(pts.astype(np.float64), search_radius=cfg["search_radius_features"])
-        np.savez_compressed(path_feat, features=feats.cpu().numpy())
+        feats = compute_features(pts.astype(np.float64), search_radius=cfg["search_radius_features"], feature_names=names)
+        save_feature_cache(path_feat, feats.cpu().numpy(), names)
 
     say("getting tiles...")
     d = np.load(path_vox)
-    feats = np.load(path_feat)["features"]
+    feats = load_feature_cache(path_feat, names)                              # ValueError: a cache written for another list
     tiler = PlotTiler(d["points"], d["labels"], feats)
     inner, outer = tile_grid(tiler.x_range, tiler.y_range, cfg["inner_edge"], cfg["outer_edge"], cfg["stride"])
     F = tiler.feats.shape[1]
@@ -293,10 +295,17 @@ def parse_args(argv=None):
     ap.add_argument("--multiplier-sor", type=float, default=None, help="statistical outlier filter: standard-deviation ratio")
     ap.add_argument("--rad", type=float, default=None, help="radius outlier filter on every tile: radius in metres (with --npoints-rad)")
     ap.add_argument("--npoints-rad", type=int, default=None, help="radius outlier filter: a point is kept with more than this many points in the ball")
+    ap.add_argument("--feature-names", nargs="+", default=list(VAL_CFG["feature_names"]),
+                    help="point features of the tiles (util/features.py), at most 5, verticality last")
     a = ap.parse_args(argv)
     for k in ("voxel_size", "search_radius_features", "inner_edge", "outer_edge", "stride"):
         if not getattr(a, k) > 0:
             ap.error(f"--{k.replace('_', '-')} must be > 0")
+    try:
+        from .features import check_feature_names
+        check_feature_names(a.feature_names, for_model=True)
+    except ValueError as e:
+        ap.error(str(e))
     return a
 
 
@@ -308,7 +317,7 @@ def main(argv=None):
         return 2
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
     cfg = dict(voxel_size=a.voxel_size, search_radius_features=a.search_radius_features, inner_edge=a.inner_edge, outer_edge=a.outer_edge,
-               stride=a.stride, sample_generator=dict(n_neigh_sor=a.n_neigh_sor, multiplier_sor=a.multiplier_sor, rad=a.rad, npoints_rad=a.npoints_rad))
+               stride=a.stride, feature_names=a.feature_names, sample_generator=dict(n_neigh_sor=a.n_neigh_sor, multiplier_sor=a.multiplier_sor, rad=a.rad, npoints_rad=a.npoints_rad))
     try:
         n = write_tiles(a.forest, cfg, logger=logging.getLogger("treelearn_amd.tiles"))
     except NotImplementedError as e:                            # a half-set filter pair
