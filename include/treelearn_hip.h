@@ -808,6 +808,54 @@ int tl_crown_structure(const int64_t* sorted_keys, int64_t n, const int64_t* kst
                        const tl_crown_params* params, double* summary, int64_t* counts, double* prof_h, int64_t* pcount, double* radii,
                        tl_stream_t stream);
 
+/* ------------------------------------------------------------------ canopy height model of a cloud (csrc/tl_canopy.hip)
+ * The per-area side of the measurements: the highest height above ground per cell (CHM) with pits and holes mended, tree tops on it,
+ * and height statistics per cell of a coarser metrics grid.  The semantics are the project's own (restated in numpy float64 in
+ * tests/canopy_restatement.py); all arithmetic is f64 in plain operators, no fma contraction.  Grids follow the terrain's rule: row-major
+ * [ny, nx], nx, ny <= 32768, nx * ny <= 2^26, a row's cell is (floor(x / cell) - ix0, floor(y / cell) - iy0).  pts f32 or f64 by dtype_f64,
+ * row stride ld >= 2 elements (x, y are read), n rows, widened exactly; h f64[n] = the height above ground of each row.  A row whose h is
+ * NaN takes part in nothing.  -0.0 counts as 0.0.
+ * tl_chm_max: keys u64[ny, nx] (overwritten) = the order-preserving image of the highest h of the cell (sign bit set for h >= 0, all bits
+ *   flipped for h < 0), 0 for a cell without a row; count i32[ny, nx] (overwritten) = its rows with a finite h.  flags i32[2] (device,
+ *   overwritten): flags[0] = 1 when an x or y is not finite, an h is infinite or a row lies outside the grid (the row is skipped and the
+ *   caller raises), else 0; flags[1] = the rows whose h is NaN.  Integer atomics only: exact, the same bits for any row order.
+ * tl_chm_owner: owner i32[ny, nx] (overwritten) = the largest label among the rows whose h equals the decoded keys[cell], -1 for a cell
+ *   without a row (or whose tying rows all have labels below 0); labels i64[n], read for the tying rows only.  *err (device) is set to 1
+ *   for a tying label outside the i32 range and is otherwise left as it is.
+ * tl_chm_pits: top f64[ny, nx] = the decoded maximum (NaN for an empty cell).  Per cell, v = the non-NaN tops among its 8 neighbours
+ *   inside the grid, k their number, m their median: sorted ascending, v[k / 2] for odd k, (v[k / 2 - 1] + v[k / 2]) / 2.0 for even k.
+ *   state u8 / chm f64[ny, nx]: a cell with rows, k >= pit_min_neighbours and m - top > pit_depth (strict): 2, m; any other cell with rows:
+ *   1, top; an empty cell with k >= pit_min_neighbours: 3, m; any other empty cell: 0, NaN.  One pass against the raw tops.
+ * tl_chm_tops: mask u8[ny, nx] = 1 for a cell whose chm is not NaN and >= min_height, when no cell within Chebyshev distance `window`
+ *   (clipped to the grid) has a greater chm and none of them with an equal chm has a smaller row-major index; else 0.
+ * tl_canopy_keys: keys i64[n] = the row-major index of the row's cell, -1 for a row whose h is NaN.  *err (device) is set to 1 when an x
+ *   or y is not finite, an h is infinite or a row lies outside the grid (the row gets -1), and is otherwise left as it is.
+ * tl_grid_metrics: one workgroup per cell over sorted_h[start[c] .. start[c + 1]): the heights of the cell's rows in ascending order
+ *   (start i64[cells + 1], ascending, within 0 .. n).  With r = the rows of the range, m = those with h > cutoff (strict; they are the
+ *   last m of the range, v[0 .. m)): counts i32[cells, 2] = r, m; metrics f64[cells, 4 + n_percentiles] = cover (m / r as doubles),
+ *   h_max (the last value), h_mean = sum(v) / m, h_sd = sqrt(sum((v - h_mean)^2) / m), then per percentile q (host array of
+ *   n_percentiles values in [0, 100], 1 .. 16 of them): pos = (q / 100.0) * (m - 1), lo = floor(pos), t = pos - lo, v[lo] + (v[min(lo + 1,
+ *   m - 1)] - v[lo]) * t.  NaN in all of them for r = 0, in all but cover and h_max for m = 0.  layers i32[cells, L]: a row with h < 0
+ *   counts in layer 0, any other in layer min(floor(h / layer), L - 1); *n_clipped (device, overwritten) = the rows of all cells with h >=
+ *   L * layer.  Sums: thread t of 256 adds v[t], v[t + 256], ... in that order, then a fixed pairwise tree over the 256 partial sums: the
+ *   same bits for the same sorted values.
+ * A null or misaligned pointer, a negative size, a grid beyond the limits, cell <= 0, pit_depth < 0, pit_min_neighbours outside 1 .. 9,
+ * window < 1, layer <= 0, L outside 1 .. 256, n_percentiles outside 1 .. 16, a percentile outside [0, 100] or a value that is not finite:
+ * TL_ERR_ARG, nothing launched.  Then n = 0 (the row passes), an empty grid or cells = 0: TL_OK without a kernel launch; tl_chm_max and
+ * tl_chm_owner still clear keys, count, flags and owner, tl_grid_metrics *n_clipped. */
+int tl_chm_max(const void* pts, int dtype_f64, int64_t ld, int64_t n, const double* h, double cell, int64_t ix0, int64_t iy0, int nx, int ny,
+               uint64_t* keys, int32_t* count, int32_t* flags, tl_stream_t stream);
+int tl_chm_owner(const void* pts, int dtype_f64, int64_t ld, int64_t n, const double* h, const int64_t* labels, double cell, int64_t ix0,
+                 int64_t iy0, int nx, int ny, const uint64_t* keys, int32_t* owner, int32_t* err, tl_stream_t stream);
+int tl_chm_pits(const uint64_t* keys, int nx, int ny, double pit_depth, int pit_min_neighbours, double* top, double* chm, uint8_t* state,
+                tl_stream_t stream);
+int tl_chm_tops(const double* chm, int nx, int ny, int window, double min_height, uint8_t* mask, tl_stream_t stream);
+int tl_canopy_keys(const void* pts, int dtype_f64, int64_t ld, int64_t n, const double* h, double cell, int64_t ix0, int64_t iy0, int nx, int ny,
+                   int64_t* keys, int32_t* err, tl_stream_t stream);
+int tl_grid_metrics(const double* sorted_h, int64_t n, const int64_t* start, int64_t cells, double cutoff, const double* percentiles,
+                    int n_percentiles, double layer, int L, double* metrics, int32_t* counts, int32_t* layers, int32_t* n_clipped,
+                    tl_stream_t stream);
+
 /* ------------------------------------------------------------------ LAS point records (csrc/tl_las.hip)
  * The record passes of the LAS reader and writer (treelearn_amd/util/las.py parses and writes the headers on the host).  The layout is
  * the ASPRS one and the rules are restated in numpy in tests/las_restatement.py; all arithmetic is f64 in plain operators, no fma

@@ -200,6 +200,12 @@ PROTOTYPES = {
     "tl_stem_profile": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _c.POINTER(StemParams), _vp, _vp, _vp, _vp, _vp]),
     "tl_crown_voxel_keys": (_i32, [_vp, _vp, _i64, _vp, _i64, _c.POINTER(CrownParams), _vp, _vp, _vp]),
     "tl_crown_structure": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _c.POINTER(CrownParams), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tl_chm_max": (_i32, [_vp, _i32, _i64, _i64, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "tl_chm_owner": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "tl_chm_pits": (_i32, [_vp, _i32, _i32, _c.c_double, _i32, _vp, _vp, _vp, _vp]),
+    "tl_chm_tops": (_i32, [_vp, _i32, _i32, _i32, _c.c_double, _vp, _vp]),
+    "tl_canopy_keys": (_i32, [_vp, _i32, _i64, _i64, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "tl_grid_metrics": (_i32, [_vp, _i64, _vp, _i64, _c.c_double, _c.POINTER(_c.c_double), _i32, _c.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
     "tl_las_decode": (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _c.c_double * 3, _c.c_double * 3, _vp, _i32, _i64, _i32, _vp]),
     "tl_las_encode": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _i64, _c.c_double * 3, _c.c_double * 3, _vp, _i64, _vp, _vp, _vp, _vp]),
     "tl_pointwise_eval_ws_bytes": (_i64, [_i64]),

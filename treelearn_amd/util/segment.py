@@ -159,7 +159,7 @@ def segment_from_pointwise(coords, offset_predictions, instance_preds, shape_cfg
 
 def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=None, return_type="original", logger=None,
                    return_pointwise=False, inventory=False, inventory_cfg=None, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None,
-                   crown=False, crown_cfg=None):
+                   crown=False, crown_cfg=None, canopy=False, canopy_cfg=None):
     """points: N x 3 or N x 4 (x y z [label]) f64, host or device.  Returns numpy arrays: coords (f64, input frame), labels (i64),
     categories (per tree 1..T, index into CATEGORIES), and with return_pointwise the arrays of pipeline.py:100-111 (ensembled rows).
     inventory=True adds result["inventory"]: util.inventory.tree_inventory of the returned coords / labels, computed on the device in
@@ -170,7 +170,14 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
     stem=True implies inventory=True and adds util.stem's columns and result["inventory"]["stem_profile"] (the circle of every slab along
     every stem); stem_cfg holds any of util.stem's parameters.
     crown=True implies inventory=True and adds util.crown's columns and result["inventory"]["crown_profile"] (rows and cells per layer,
-    crown radii per sector); crown_cfg holds any of util.crown's parameters."""
+    crown radii per sector); crown_cfg holds any of util.crown's parameters.
+    canopy=True implies terrain=True and adds result["canopy"] (util.canopy: the canopy height model, tree tops and grid metrics of the
+    returned cloud, from the same height_above_ground; the un-centred Canopy.to_host()) and result["stand"] (util.canopy.stand_summary,
+    with the inventory when one is computed); canopy_cfg holds any of util.canopy's parameters."""
+    if canopy:
+        from .canopy import canopy_model, check_params as check_canopy, stand_summary
+        canopy_cfg = check_canopy(canopy_cfg)                                         # before any GPU work
+        terrain = True
     if crown:
         from .crown import check_params as check_crown
         crown_cfg = check_crown(crown_cfg)                                            # before any GPU work
@@ -234,11 +241,16 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
         _log(logger, "computing the terrain model")
         dtm = terrain_model(r["coords"], r["labels"], offset=mean, **terrain_cfg)
         result["terrain"] = dtm.to_host()
-        result["height_above_ground"] = host(dtm.height_above_ground(r["coords"]))
+        hag = dtm.height_above_ground(r["coords"])
+        result["height_above_ground"] = host(hag)
     if inventory:
         _log(logger, "computing the tree inventory")
         result["inventory"] = tree_inventory(r["coords"], r["labels"], offset=mean, terrain=dtm, stem=stem, stem_cfg=stem_cfg if stem else None,
                                              crown=crown, crown_cfg=crown_cfg if crown else None, **inventory_cfg)
+    if canopy:
+        _log(logger, "computing the canopy height model")
+        result["canopy"] = canopy_model(r["coords"], labels=r["labels"], height_above_ground=hag, offset=mean, **canopy_cfg).to_host()
+        result["stand"] = stand_summary(result["canopy"], result.get("inventory"))
     if return_pointwise:
         pw = dict(coords=coords, offset_predictions=off, offset_labels=offl, semantic_prediction_logits=sem, semantic_labels=seml,
                   instance_labels=instl, backbone_feats=bb, input_feats=infeat, instance_preds=inst, instance_preds_after_initial_clustering=initial)
@@ -298,7 +310,8 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
     pointwise_results/pointwise_results.npz + cluster_coords_initial / cluster_coords (first format) when the result holds them;
     tree_inventory.csv (util.inventory.write_inventory, with the category names) when the result holds an inventory; terrain.npz
     (util.terrain.write_terrain) and height_above_ground.npy when it holds a terrain; stem_profiles.npz (util.stem.write_stem_profiles) when
-    the inventory holds stem profiles; crown_profiles.npz (util.crown.write_crown_profiles) when it holds crown profiles."""
+    the inventory holds stem profiles; crown_profiles.npz (util.crown.write_crown_profiles) when it holds crown profiles; canopy.npz and stand.json
+    (util.canopy.write_canopy, write_stand) when the result holds a canopy."""
     save_formats = list(save_formats)
     check_formats(save_formats)
     coords, labels = np.asarray(result["coords"], np.float64), np.asarray(result["labels"], np.int64)
@@ -353,6 +366,11 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
         os.makedirs(out_dir, exist_ok=True)
         write_terrain(os.path.join(out_dir, "terrain.npz"), result["terrain"])
         np.save(os.path.join(out_dir, "height_above_ground.npy"), np.asarray(result["height_above_ground"], np.float64))
+    if "canopy" in result:
+        from .canopy import write_canopy, write_stand
+        os.makedirs(out_dir, exist_ok=True)
+        write_canopy(os.path.join(out_dir, "canopy.npz"), result["canopy"])
+        write_stand(os.path.join(out_dir, "stand.json"), result["stand"])
     if save_pointwise and "pointwise" in result:
         pw = result["pointwise"]
         pdir = os.path.join(out_dir, "pointwise_results")
@@ -422,12 +440,16 @@ def parse_args(argv=None):
     ap.add_argument("--crown", action="store_true", help="write crown_profiles.npz and add the crown columns to tree_inventory.csv (implies --inventory)")
     from . import crown as _crown
     _crown.add_arguments(ap)
+    ap.add_argument("--canopy", action="store_true", help="write canopy.npz (canopy height model, tree tops, grid metrics) and stand.json (implies --terrain)")
+    from . import canopy as _canopy
+    _canopy.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         check_params(params_of(a))
         _terrain.check_params(_terrain.params_of(a))
         _stem.check_params(_stem.params_of(a))
         _crown.check_params(_crown.params_of(a))
+        _canopy.check_params(_canopy.params_of(a))
     except ValueError as e:
         ap.error(str(e))
     check_formats(a.formats)
@@ -468,13 +490,14 @@ def main(argv=None):
                     tau_vert=a.tau_vert, tau_off=a.tau_off)
     shape = dict(SHAPE_CFG, alpha=a.alpha, buffer_size_to_determine_edge_trees=a.edge_buffer, outer_remove=a.outer_remove)
     with torch.no_grad():
-        from . import crown as _crown, stem as _stem, terrain as _terrain
+        from . import canopy as _canopy, crown as _crown, stem as _stem, terrain as _terrain
         from .inventory import params_of
         res = segment_forest(points, model, sample, grouping, shape, a.return_type, logger, return_pointwise=a.save_pointwise,
                              inventory=a.inventory, inventory_cfg=params_of(a) if a.inventory or a.stem or a.crown else None,
-                             terrain=a.terrain, terrain_cfg=_terrain.params_of(a) if a.terrain else None,
+                             terrain=a.terrain, terrain_cfg=_terrain.params_of(a) if a.terrain or a.canopy else None,
                              stem=a.stem, stem_cfg=_stem.params_of(a) if a.stem else None,
-                             crown=a.crown, crown_cfg=_crown.params_of(a) if a.crown else None)
+                             crown=a.crown, crown_cfg=_crown.params_of(a) if a.crown else None,
+                             canopy=a.canopy, canopy_cfg=_canopy.params_of(a) if a.canopy else None)
     plot_name = os.path.splitext(os.path.basename(a.forest))[0]
     save_results(res, a.out, plot_name, a.formats, save_treewise=not a.no_treewise, save_pointwise=a.save_pointwise)
     cats = np.bincount(res["categories"], minlength=3)
