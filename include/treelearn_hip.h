@@ -808,6 +808,53 @@ int tl_crown_structure(const int64_t* sorted_keys, int64_t n, const int64_t* kst
                        const tl_crown_params* params, double* summary, int64_t* counts, double* prof_h, int64_t* pcount, double* radii,
                        tl_stream_t stream);
 
+/* ------------------------------------------------------------------ branch structure of a labelled cloud (csrc/tl_skeleton.hip)
+ * What is inside the crown: the geodesic distance of every voxel of a tree from its stem base along the tree's own voxels, the level sets
+ * of that distance cut into connected components (the skeleton nodes) and every node's parent.  The semantics are the project's own and
+ * have no reference call site: tests/branches_restatement.py restates them in Python.  Every result but the node centroids is an integer;
+ * the f64 arithmetic (floor(coordinate / voxel), the centroid division) is in plain operators, no fma contraction.  The rows and `tree`
+ * f64[n_trees, 4] = px, py, z_ref, z_top are those of the crown structure above.
+ * A voxel is (ix, iy, iz) = floor((x, y, z) / voxel), one grid for all trees; (ipx, ipy, izr) = floor((px, py, z_ref) / voxel).
+ * tl_skel_voxel_keys: keys i64[n] = (t << 35) | (ix_rel << 23) | (iy_rel << 11) | iz_rel for a row of tree t = label - 1, ix_rel = ix - ipx +
+ *   2048, the same in y, iz_rel = iz - izr; else -1: a label outside 1 .. n_trees, a tree whose px, py or z_ref is not finite, or a row
+ *   with iz < izr.  *err (device) = 1 when a row of a label in 1 .. n_trees has a coordinate that is not finite, or a row with iz >= izr
+ *   has |ix - ipx| > 2047, |iy - ipy| > 2047 or iz_rel >= 2047 (the row gets -1 and the caller raises), else 0.  Every range is tested on
+ *   the f64 value.  The caller sorts the keys, drops the repeats and the -1, and takes kstart i64[n_trees + 1]: kstart[t] = the first key
+ *   >= t << 35.  voxel_keys i64[n] below are those distinct ascending keys; a voxel is its index (n < 2^31), and index order is key order.
+ * The graph: an edge joins two voxels of one tree with max(|dx|, |dy|, |dz|) <= reach, of weight floor(sqrt(10000 * (dx^2 + dy^2 + dz^2))):
+ *   100, 141, 173 (reach 1), 200, 223, 244, 282, 300, 346 (reach 2).  Neighbours are looked up inside [kstart[t], kstart[t + 1]) only.
+ * tl_skel_distance: one workgroup per tree.  Sources: of the voxels with |ix_rel - 2048|, |iy_rel - 2048| <= base_reach, those fewer than
+ *   base_layers above the lowest of them.  d i32[n] = the shortest-path distance from the source set, 0 on sources, -1 for a voxel no path
+ *   reaches, for every voxel of a tree without a source and of a tree of more than max_voxels voxels.  rounds i32[n_trees] = the number
+ *   of bucket rounds the tree took (0 without a skeleton).  The distance is unique: the same bits whatever the order of the atomics.
+ * tl_skel_nodes: bin(v) = d(v) / (100 * level).  A node is a connected component, under the edges above, of reached voxels of one bin.
+ *   parent i32[n] (overwritten) = a union-find forest whose roots are the nodes' smallest voxels; acc i64[n, 4] (overwritten) = at a root:
+ *   the node's voxels, the sums of their ix_rel, iy_rel, iz_rel, elsewhere 0; vstar i64[n] (overwritten) = at a root: (d << 32) | index of
+ *   the node's voxel with the smallest (d, key), elsewhere -1.
+ * tl_skel_links: one thread per node.  roots i32[n_nodes] = the root voxels in the caller's node order (tree, bin, root ascending),
+ *   node_id i32[n] = the node's index in that order at a root, node_start i64[n_trees + 1] = the first node of every tree.  node_xyz
+ *   f64[n_nodes, 3] = ((double)sum / (double)count + 0.5) * voxel per axis, the sums taken to absolute voxel indices in integers;
+ *   node_bin i32, node_count i64; node_parent i32 = -1 for a node of bin 0, else the node (index local to the tree) of the predecessor of
+ *   the node's first voxel v*: its neighbour u with d(u) + w(u, v*) = d(v*) of the smallest key.  It has a smaller bin.
+ * A null or misaligned pointer, a negative size, n >= 2^31, n_nodes > n, n_trees >= 2^21 or a parameter outside its constraint (voxel > 0,
+ * min_branch, min_height >= 0, all finite; reach 1 or 2; base_reach in 0 .. 2047; base_layers >= 1; level in 1 .. 10^6; max_voxels >= 1):
+ * TL_ERR_ARG, nothing launched.  Then n = 0 or n_trees = 0 (and n_nodes = 0 for tl_skel_links): TL_OK without a launch, outputs and *err
+ * untouched.  d stays below 2^31 for max_voxels <= 2^22 (346 per step), which util.branches enforces. */
+typedef struct tl_skel_params {
+  double voxel, min_branch, min_height;
+  int64_t reach, base_reach, base_layers, level, max_voxels;
+} tl_skel_params;
+int tl_skel_voxel_keys(const double* sorted_xyz, const int64_t* sorted_label, int64_t n, const double* tree, int64_t n_trees,
+                       const tl_skel_params* params, int64_t* keys, int32_t* err, tl_stream_t stream);
+int tl_skel_distance(const int64_t* voxel_keys, int64_t n, const int64_t* kstart, int64_t n_trees, const tl_skel_params* params, int32_t* d,
+                     int32_t* rounds, tl_stream_t stream);
+int tl_skel_nodes(const int64_t* voxel_keys, int64_t n, const int64_t* kstart, int64_t n_trees, const tl_skel_params* params, const int32_t* d,
+                  int32_t* parent, int64_t* acc, int64_t* vstar, tl_stream_t stream);
+int tl_skel_links(const int64_t* voxel_keys, int64_t n, const int64_t* kstart, const double* tree, int64_t n_trees,
+                  const tl_skel_params* params, const int32_t* d, int32_t* parent, const int64_t* acc, const int64_t* vstar, const int32_t* roots,
+                  int64_t n_nodes, const int32_t* node_id, const int64_t* node_start, double* node_xyz, int32_t* node_parent, int32_t* node_bin,
+                  int64_t* node_count, tl_stream_t stream);
+
 /* ------------------------------------------------------------------ canopy height model of a cloud (csrc/tl_canopy.hip)
  * The per-area side of the measurements: the highest height above ground per cell (CHM) with pits and holes mended, tree tops on it,
  * and height statistics per cell of a coarser metrics grid.  The semantics are the project's own (restated in numpy float64 in

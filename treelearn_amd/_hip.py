@@ -105,6 +105,11 @@ class CrownParams(_c.Structure):           # tl_crown_params
     _fields_ = [(k, _c.c_double) for k in ("layer", "cell", "min_height")] + [(k, _i64) for k in ("max_layers", "base_percent", "max_gap")]
 
 
+class SkeletonParams(_c.Structure):        # tl_skel_params
+    _fields_ = [(k, _c.c_double) for k in ("voxel", "min_branch", "min_height")] + \
+               [(k, _i64) for k in ("reach", "base_reach", "base_layers", "level", "max_voxels")]
+
+
 _I4 = _i32 * 4
 _I3 = _i32 * 3
 
@@ -200,6 +205,11 @@ PROTOTYPES = {
     "tl_stem_profile": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _c.POINTER(StemParams), _vp, _vp, _vp, _vp, _vp]),
     "tl_crown_voxel_keys": (_i32, [_vp, _vp, _i64, _vp, _i64, _c.POINTER(CrownParams), _vp, _vp, _vp]),
     "tl_crown_structure": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _c.POINTER(CrownParams), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tl_skel_voxel_keys": (_i32, [_vp, _vp, _i64, _vp, _i64, _c.POINTER(SkeletonParams), _vp, _vp, _vp]),
+    "tl_skel_distance": (_i32, [_vp, _i64, _vp, _i64, _c.POINTER(SkeletonParams), _vp, _vp, _vp]),
+    "tl_skel_nodes": (_i32, [_vp, _i64, _vp, _i64, _c.POINTER(SkeletonParams), _vp, _vp, _vp, _vp, _vp]),
+    "tl_skel_links": (_i32, [_vp, _i64, _vp, _vp, _i64, _c.POINTER(SkeletonParams), _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp]),
     "tl_chm_max": (_i32, [_vp, _i32, _i64, _i64, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "tl_chm_owner": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "tl_chm_pits": (_i32, [_vp, _i32, _i32, _c.c_double, _i32, _vp, _vp, _vp, _vp]),

@@ -31,7 +31,10 @@ With stem=True (util.stem) the seven STEM_COLUMNS follow them, and 
 along every stem: the stage runs on the same label-sorted rows and tree table, heights from z_ground with a terrain, else from z_low.
 
 With crown=True (util.crown) the fourteen CROWN_COLUMNS follow them, and the key "crown_profile" holds the rows and cells of
-every layer of every tree and its crown radii in eight sectors: the same rows, table and reference height."""
+every layer of every tree and its crown radii in eight sectors: the same rows, table and reference height.
+
+With branches=True (util.branches) the thirteen BRANCH_COLUMNS follow them, and the key "skeleton" holds the node table of
+every tree's skeleton: the same rows, table and reference height."""
 import argparse
 import csv
 import sys
@@ -108,7 +111,8 @@ def _device_inputs(coords, labels):
 
 
 def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh_max_radius=1.0, dbh_min_points=8, crown_cell=0.25,
-                   offset=None, stages=None, terrain=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None):
+                   offset=None, stages=None, terrain=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None, branches=False,
+                   branch_cfg=None):
     """coords [N, 3] float32 or float64 (a row stride of 3 or 4 elements is read in place), labels [N] integers; numpy arrays or tensors,
     on the host or the device.  Returns a dict of numpy arrays of length T = max(label), keyed by COLUMNS (tree_id = 1..T).
     `offset` (3 values) is added to x, y, z, z_low, z_top, dbh_x, dbh_y at the end -- the un-centring of segment_forest.
@@ -118,7 +122,12 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     `stem`: True adds util.stem's STEM_COLUMNS after them and "stem_profile", a dict of [T, S] arrays (h, x, y, r, rmse, n, state;
     `offset` is added to its x, y); stem_cfg holds any of util.stem's parameters.
     `crown`: True adds util.crown's CROWN_COLUMNS after them and "crown_profile", a dict of [T, L] arrays (h, n, cells) and radii [T, 8]
-    (`offset` is added to crown_x, crown_y); crown_cfg holds any of util.crown's parameters."""
+    (`offset` is added to crown_x, crown_y); crown_cfg holds any of util.crown's parameters.
+    `branches`: True adds util.branches' BRANCH_COLUMNS after them and "skeleton", the ragged node table of every tree's skeleton
+    (`offset` is added to its xyz); branch_cfg holds any of util.branches' parameters."""
+    if branches:
+        from . import branches as _branches
+        branch_cfg = _branches.check_params(branch_cfg)                               # before any GPU work
     if crown:
         from . import crown as _crown
         crown_cfg = _crown.check_params(crown_cfg)                                    # before any GPU work
@@ -186,13 +195,15 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
         _hip.check(L.tl_crown_count(_hip.ptr(keys), m, T, _hip.ptr(cells), _hip.stream()), "tl_crown_count")
     mark("crown keys + count")
 
-    if stem or crown:
+    if stem or crown or branches:
         z_ref = gtable[:, 0] if terrain is not None else table[:, 0]
         tree = torch.stack([table[:, 3], table[:, 4], z_ref, table[:, 1]], 1).contiguous()
     if stem:
         stem_dev = _stem.stem_stage(xyz, kept_lab, T, tree, stem_cfg, mark)
     if crown:
         *crown_dev, crown_err = _crown.crown_stage(xyz, kept_lab, T, tree, crown_cfg, mark)
+    if branches:
+        branch_dev = _branches.branch_stage(xyz, kept_lab, T, tree, branch_cfg, mark)
 
     table_h, counts_h, cells_h = table.cpu().numpy(), counts.cpu().numpy(), cells.cpu().numpy()
     if terrain is not None:
@@ -202,12 +213,18 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     if crown:
         crown_out = _crown.to_columns(*(t.cpu().numpy() for t in crown_dev), off)
         crown_bad = crown_err is not None and int(crown_err.item())
+    if branches:
+        branch_h = {k: branch_dev[k].cpu().numpy() for k in ("kstart", "node_start", "xyz", "parent", "bin", "count")}
+        branch_zref = tree[:, 2].cpu().numpy()
+        branch_bad = branch_dev["err"] is not None and int(branch_dev["err"].item())
     bad = err is not None and int(err.item())
     mark("D2H")
     if bad:
         raise ValueError(f"a coordinate is not finite or lies beyond 2^20 crown cells of {p['crown_cell']} m from the origin: centre the cloud")
     if crown and crown_bad:
         raise _crown.crown_error(crown_cfg)
+    if branches and branch_bad:
+        raise _branches.branch_error(branch_cfg)
 
     out = {k: np.ascontiguousarray(table_h[:, j]) for j, k in enumerate(_TABLE)}
     out["tree_id"] = np.arange(1, T + 1, dtype=np.int64)
@@ -227,6 +244,10 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     if crown:
         out.update(crown_out)
         stem_keys = stem_keys + _crown.CROWN_COLUMNS + ("crown_profile",)
+    if branches:
+        out.update(_branches.to_columns(branch_h, branch_zref, branch_cfg, off))
+        mark("branch decomposition")
+        stem_keys = stem_keys + _branches.BRANCH_COLUMNS + ("skeleton",)
     if terrain is None:
         return {k: out[k] for k in COLUMNS + stem_keys}
     out.update({k: np.ascontiguousarray(gtable_h[:, j]) for j, k in enumerate(_GROUND_TABLE)})
@@ -237,12 +258,13 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     return {k: out[k] for k in COLUMNS + GROUND_COLUMNS + stem_keys}
 
 
-def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None, **params):
+def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None, branches=False,
+                    branch_cfg=None, **params):
     """The inventory of an N x 4 cloud (x y z label), as the command line computes it: the coordinates are centred on their float64 mean
     on the device, as segment_forest centres its input, and the mean is handed back as `offset`.  terrain=True builds the terrain of
     the label-0 rows in the same frame (util.terrain.terrain_model, parameters in terrain_cfg) and adds the GROUND_COLUMNS; stem=True
     adds util.stem's STEM_COLUMNS and "stem_profile" (parameters in stem_cfg); crown=True adds util.crown's CROWN_COLUMNS and
-    "crown_profile" (parameters in crown_cfg)."""
+    "crown_profile" (parameters in crown_cfg); branches=True adds util.branches' BRANCH_COLUMNS and "skeleton" (parameters in branch_cfg)."""
     import torch
     pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points))
     if pts.ndim != 2 or pts.shape[1] != 4:
@@ -257,30 +279,36 @@ def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cf
     if crown:
         from .crown import check_params as check_crown
         crown_cfg = check_crown(crown_cfg)
+    extra = {}
+    if branches:
+        from .branches import check_params as check_branches
+        extra = dict(branches=True, branch_cfg=check_branches(branch_cfg))
     if not torch.cuda.is_available():
         raise RuntimeError("treelearn_amd.util.inventory runs on the GPU (tl_tree_inventory); there is no CPU fallback")
     pts = pts.to("cuda")
     xyz, lab = pts[:, :3].to(torch.float64), pts[:, 3].to(torch.int64)
     if len(xyz) == 0:
         return tree_inventory(xyz, lab, terrain=terrain_model(xyz, lab, **terrain_cfg) if terrain else None, stem=stem, stem_cfg=stem_cfg, crown=crown,
-                              crown_cfg=crown_cfg, **params)
+                              crown_cfg=crown_cfg, **extra, **params)
     mean = xyz.mean(0)
     centred = xyz - mean
     return tree_inventory(centred, lab, offset=mean, terrain=terrain_model(centred, lab, **terrain_cfg) if terrain else None, stem=stem,
-                          stem_cfg=stem_cfg, crown=crown, crown_cfg=crown_cfg, **params)
+                          stem_cfg=stem_cfg, crown=crown, crown_cfg=crown_cfg, **extra, **params)
 
 
 def write_inventory(path, inv, categories=None):
     """CSV: a header row, then one row per tree; floats as repr (they read back to the same bits), NaN as `nan`.  `categories` (per tree:
     index into segment.CATEGORIES) adds a `category` column of names.  The columns are those the dict holds: COLUMNS, and GROUND_COLUMNS
     after them when the inventory was taken with a terrain, then util.stem's STEM_COLUMNS when it was taken with stem=True, then
-    util.crown's CROWN_COLUMNS when it was taken with crown=True (each group only when the dict holds all of it)."""
+    util.crown's CROWN_COLUMNS when it was taken with crown=True, then util.branches' BRANCH_COLUMNS when it was taken with branches=True
+    (each group only when the dict holds all of it)."""
+    from .branches import BRANCH_COLUMNS, BRANCH_INT_COLUMNS
     from .crown import CROWN_COLUMNS, CROWN_INT_COLUMNS
     from .stem import STEM_COLUMNS
     T = len(inv["tree_id"])
     columns = COLUMNS + (GROUND_COLUMNS if all(k in inv for k in GROUND_COLUMNS) else ()) + (STEM_COLUMNS if all(k in inv for k in STEM_COLUMNS) else ()) + \
-        (CROWN_COLUMNS if all(k in inv for k in CROWN_COLUMNS) else ())
-    ints = INT_COLUMNS + ("dbh_ag_n", "stem_slices") + CROWN_INT_COLUMNS
+        (CROWN_COLUMNS if all(k in inv for k in CROWN_COLUMNS) else ()) + (BRANCH_COLUMNS if all(k in inv for k in BRANCH_COLUMNS) else ())
+    ints = INT_COLUMNS + ("dbh_ag_n", "stem_slices") + CROWN_INT_COLUMNS + BRANCH_INT_COLUMNS
     names = None
     if categories is not None:
         from .segment import CATEGORIES
@@ -325,12 +353,16 @@ def main(argv=None):
     ap.add_argument("--crown", action="store_true", help="add the crown columns: crown base, length, ratio, volume, projection area, centroid and radii")
     from . import crown as _crown
     _crown.add_arguments(ap)
+    ap.add_argument("--branches", action="store_true", help="add the branch columns: skeleton size and length, axis, branch count, length and order, first branch")
+    from . import branches as _branches
+    _branches.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         params = check_params(params_of(a))
         terrain_cfg = _terrain.check_params(_terrain.params_of(a))
         stem_cfg = _stem.check_params(_stem.params_of(a))
         crown_cfg = _crown.check_params(_crown.params_of(a))
+        branch_cfg = _branches.check_params(_branches.params_of(a))
     except ValueError as e:
         ap.error(str(e))
     if not os.path.exists(a.forest):
@@ -340,7 +372,8 @@ def main(argv=None):
     if data.shape[1] != 4:
         ap.error(f"--forest {a.forest}: expected N x 4 (x y z label), got {data.shape}")
     inv = cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, stem=a.stem, stem_cfg=stem_cfg if a.stem else None,
-                          crown=a.crown, crown_cfg=crown_cfg if a.crown else None, **params)
+                          crown=a.crown, crown_cfg=crown_cfg if a.crown else None, branches=a.branches,
+                          branch_cfg=branch_cfg if a.branches else None, **params)
     write_inventory(a.out, inv)
     ok = int(np.isfinite(inv["dbh"]).sum())
     print(f"{a.forest}: {len(data)} points, {len(inv['tree_id'])} trees, {ok} with a DBH -> {a.out}")
