@@ -855,6 +855,38 @@ int tl_skel_links(const int64_t* voxel_keys, int64_t n, const int64_t* kstart, c
                   int64_t n_nodes, const int32_t* node_id, const int64_t* node_start, double* node_xyz, int32_t* node_parent, int32_t* node_bin,
                   int64_t* node_count, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ cylinder model of the skeleton (csrc/tl_wood.hip)
+ * How thick the wood is: one Kasa circle fit per skeleton node of the branch structure above, in the plane across the node's axis.  The
+ * semantics are the project's own (restated in Python in tests/wood_restatement.py); all arithmetic is f64 in plain operators, no fma
+ * contraction.  The radii along the branches, the frusta and the columns are read off the node table on the host (util/wood.py).
+ * tl_wood_row_nodes: one thread per gathered row.  row_keys i64[m] = the keys tl_skel_voxel_keys gave the rows; voxel_keys i64[n_voxels], d
+ *   i32[n_voxels], uf_parent i32[n_voxels] (the union-find forest of tl_skel_nodes; read, paths are not compressed) and node_id
+ *   i32[n_voxels] (the node of a root voxel) as tl_skel_links takes them.  row_node i32[m] = the node (global index) of the row's voxel when
+ *   the key is >= 0, is found in voxel_keys and that voxel is reached (d >= 0); else -1.
+ * The caller sorts row_node stably: perm i64[m] = the permutation, range_start i64[n_nodes + 1]: range_start[i] = the first position of the
+ *   sorted values that is >= i, so that perm[range_start[i] .. range_start[i + 1]) are the rows of node i.
+ * tl_wood_fit: one wavefront per node.  node_xyz f64[n_nodes, 3], node_parent i32[n_nodes] (local to the tree, -1 for a root), node_start
+ *   i64[n_trees + 1] are the node table of tl_skel_links.  Axis a: for a node with a parent at the centroid distance seg = sqrt(dx dx + dy dy
+ *   + dz dz) > 0: (c - c_parent) / seg; else (0, 0, 1).  Basis: k = the index of the smallest |a_k| (the first among equals), w = a x e_k,
+ *   e1 = w / |w|, e2 = a x e1.  Over the node's rows p: q = p - c, u = q . e1, v = q . e2.  n = the rows; with n >= min_points the Kasa
+ *   circle (cu, cv, r) of the (u, v) and rmse = sqrt(sum((sqrt((u - cu)^2 + (v - cv)^2) - r)^2) / n).  The fit is accepted when the solve
+ *   succeeded, min_radius <= r <= max_radius, rmse <= max_rmse and sqrt(cu^2 + cv^2) <= r.  state i32[n_nodes] = 0 for n < min_points, 1
+ *   accepted, 2 rejected; count i64[n_nodes] = n; radius_fit, rmse f64[n_nodes] and centre f64[n_nodes, 3] = c + cu e1 + cv e2 are NaN
+ *   unless state is 1; axis f64[n_nodes, 3] = a.  Sums: lane l of 64 adds the rows l, l + 64, ... of the node's range in that order,
+ *   then a fixed xor butterfly: the same bits for the same permutation.  max_growth and dbh_height are the host rules' (util/wood.py).
+ * A null or misaligned pointer, a negative size, n_voxels or n_nodes >= 2^31, n_nodes > n_voxels (tl_wood_row_nodes) or a parameter outside
+ * its constraint (min_points >= 3; max_rmse >= 0; 0 <= min_radius < max_radius; max_growth >= 1; dbh_height >= 0; all finite): TL_ERR_ARG,
+ * nothing launched.  Then m = 0 or n_nodes = 0 (or n_trees = 0 for tl_wood_fit): TL_OK without a launch, outputs untouched. */
+typedef struct tl_wood_params {
+  double max_rmse, min_radius, max_radius, max_growth, dbh_height;
+  int64_t min_points;
+} tl_wood_params;
+int tl_wood_row_nodes(const int64_t* row_keys, int64_t m, const int64_t* voxel_keys, int64_t n_voxels, const int32_t* d, int32_t* uf_parent,
+                      const int32_t* node_id, int64_t n_nodes, int32_t* row_node, tl_stream_t stream);
+int tl_wood_fit(const double* sorted_xyz, int64_t m, const int64_t* perm, const int64_t* range_start, const double* node_xyz,
+                const int32_t* node_parent, const int64_t* node_start, int64_t n_trees, int64_t n_nodes, const tl_wood_params* params,
+                double* radius_fit, int64_t* count, double* rmse, int32_t* state, double* centre, double* axis, tl_stream_t stream);
+
 /* ------------------------------------------------------------------ canopy height model of a cloud (csrc/tl_canopy.hip)
  * The per-area side of the measurements: the highest height above ground per cell (CHM) with pits and holes mended, tree tops on it,
  * and height statistics per cell of a coarser metrics grid.  The semantics are the project's own (restated in numpy float64 in

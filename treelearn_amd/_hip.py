@@ -110,6 +110,10 @@ class SkeletonParams(_c.Structure):        # tl_skel_params
                [(k, _i64) for k in ("reach", "base_reach", "base_layers", "level", "max_voxels")]
 
 
+class WoodParams(_c.Structure):            # tl_wood_params
+    _fields_ = [(k, _c.c_double) for k in ("max_rmse", "min_radius", "max_radius", "max_growth", "dbh_height")] + [("min_points", _i64)]
+
+
 _I4 = _i32 * 4
 _I3 = _i32 * 3
 
@@ -210,6 +214,8 @@ PROTOTYPES = {
     "tl_skel_nodes": (_i32, [_vp, _i64, _vp, _i64, _c.POINTER(SkeletonParams), _vp, _vp, _vp, _vp, _vp]),
     "tl_skel_links": (_i32, [_vp, _i64, _vp, _vp, _i64, _c.POINTER(SkeletonParams), _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp]),
+    "tl_wood_row_nodes": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "tl_wood_fit": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(WoodParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tl_chm_max": (_i32, [_vp, _i32, _i64, _i64, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "tl_chm_owner": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "tl_chm_pits": (_i32, [_vp, _i32, _i32, _c.c_double, _i32, _vp, _vp, _vp, _vp]),

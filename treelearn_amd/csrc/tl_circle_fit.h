@@ -1,6 +1,6 @@
 // The circle fit that the inventory and the stem profiles share: the workgroup sum, the Kasa solve and the slice fit
-// of one contiguous row range, for workgroups of kBlock threads.  Internal to tl_inventory.hip and tl_stem.hip.  Every formula is f64 in
-// plain operators under the pragma below (no contraction into fma).
+// of one contiguous row range, for workgroups of kBlock threads.  Internal to tl_inventory.hip and tl_stem.hip; tl_wood.hip
+// takes the Kasa solve and the wavefront sum.  Every formula is f64 in plain operators under the pragma below (no contraction into fma).
 #pragma once
 #include "tl_common.h"
 
@@ -29,6 +29,15 @@ __device__ __forceinline__ void block_sum(double (&v)[K], double* __restrict__ s
     for (int w = 1; w < kWaves; ++w) a = a + s[w * K + k];
     v[k] = a;
   }
+}
+
+// Sum of K per-lane values over one wavefront, the same in every lane: the xor butterfly alone.  No LDS, no barrier: the waves of a
+// workgroup may call it independently (csrc/tl_wood.hip: one wave per node).
+template <int K>
+__device__ __forceinline__ void wave_sum(double (&v)[K]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    for (int o = 32; o > 0; o >>= 1) v[k] = v[k] + __shfl_xor(v[k], o);
 }
 
 struct Fit { double cx, cy, r; int ok; };

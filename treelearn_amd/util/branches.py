@@ -1,7 +1,7 @@
 """Branch structure of a segmented forest on the device: the skeleton of every tree, how long its wood is, how many branches it has, of
 which order, and where the first one leaves the stem.
 
-    python -m treelearn_amd.util.branches --forest labelled.npy|npz|txt|las --out skeletons.npz [--csv trees.csv] [--terrain] [--branch-voxel 0.1 ...]
+    python -m treelearn_amd.util.branches --forest labelled.npy|npz|txt|las --out skeletons.npz [--csv trees.csv] [--terrain] [--wood] [--branch-voxel 0.1 ...]
 
 The semantics are the project's own; tests/branches_restatement.py states them in plain Python.  The stage runs inside
 util.inventory.tree_inventory(..., branches=True) on the label-sorted rows and the tree table that function already holds on the device.
@@ -105,7 +105,8 @@ def branch_stage(xyz, kept_lab, T, tree, p, mark):
     """The stage on the device.  xyz f64 [m, 3]: the gathered rows in label order, kept_lab i64 [m]: their labels, tree f64 [T, 4] = px, py,
     z_ref, z_top per tree, p: checked parameters, mark(name): closes a timed stage.  Returns a dict of device tensors: voxel_keys i64 [U]
     (the distinct voxels, ascending), kstart i64 [T + 1], d i32 [U], rounds i32 [T], node_start i64 [T + 1], xyz f64 [M, 3], parent, bin
-    i32 [M], count i64 [M], and err i32 [1] (or None: no rows); the caller raises branch_error() when err reads non-zero."""
+    i32 [M], count i64 [M], and err i32 [1] (or None: no rows); the caller raises branch_error() when err reads non-zero.  For util.wood
+    also row_keys i64 [m] (every row's voxel key), uf_parent i32 [U] (the union-find forest of the nodes) and node_id i32 [U]."""
     import torch
     from .. import _hip
     lib, dev, m = _hip.lib(), xyz.device, len(xyz)
@@ -113,11 +114,12 @@ def branch_stage(xyz, kept_lab, T, tree, p, mark):
     i64, i32 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.int32, device=dev)
     out = dict(voxel_keys=torch.zeros(0, **i64), kstart=torch.zeros(T + 1, **i64), d=torch.zeros(0, **i32), rounds=torch.zeros(T, **i32),
                node_start=torch.zeros(T + 1, **i64), xyz=torch.zeros((0, 3), dtype=torch.float64, device=dev), parent=torch.zeros(0, **i32),
-               bin=torch.zeros(0, **i32), count=torch.zeros(0, **i64), err=None)
+               bin=torch.zeros(0, **i32), count=torch.zeros(0, **i64), err=None, row_keys=torch.zeros(0, **i64), uf_parent=torch.zeros(0, **i32),
+               node_id=torch.zeros(0, **i32))
     U = 0
     if T and m:
         keys = torch.empty(m, **i64)
-        out["err"] = torch.zeros(1, **i32)
+        out["err"], out["row_keys"] = torch.zeros(1, **i32), keys
         _hip.check(lib.tl_skel_voxel_keys(_hip.ptr(xyz), _hip.ptr(kept_lab), m, _hip.ptr(tree), T, sp, _hip.ptr(keys), _hip.ptr(out["err"]),
                                           _hip.stream()), "tl_skel_voxel_keys")
         mark(STAGES[0])
@@ -141,6 +143,7 @@ def branch_stage(xyz, kept_lab, T, tree, p, mark):
     parent, acc, vstar = torch.empty(U, **i32), torch.empty((U, 4), **i64), torch.empty(U, **i64)
     _hip.check(lib.tl_skel_nodes(_hip.ptr(vk), U, _hip.ptr(kstart), T, sp, _hip.ptr(d), _hip.ptr(parent), _hip.ptr(acc), _hip.ptr(vstar),
                                  _hip.stream()), "tl_skel_nodes")
+    out["uf_parent"] = parent
     mark(STAGES[3])
     # the node order: (tree, bin, root) ascending -- the roots come out ascending, one stable sort by (tree, bin) does the rest
     roots = torch.nonzero((parent == torch.arange(U, **i32)) & (d >= 0)).reshape(-1)
@@ -151,6 +154,7 @@ def branch_stage(xyz, kept_lab, T, tree, p, mark):
         roots, troot = roots[order], troot[order].contiguous()
         node_id = torch.full((U,), -1, **i32)
         node_id[roots] = torch.arange(M, **i32)
+        out["node_id"] = node_id
         out["node_start"] = torch.searchsorted(troot, tree_ids).contiguous()
         out["xyz"], out["count"] = torch.empty((M, 3), dtype=torch.float64, device=dev), torch.empty(M, **i64)
         out["parent"], out["bin"] = torch.empty(M, **i32), torch.empty(M, **i32)
@@ -253,7 +257,7 @@ def write_skeletons(path, inv):
 
 
 def add_arguments(ap):
-    """One --branch-... option per parameter (shared with util.segment, util.inventory, util.stem and util.crown)."""
+    """One --branch-... option per parameter (shared with util.segment, util.inventory, util.stem, util.crown and util.wood)."""
     for k, v in BRANCH_DEFAULTS.items():
         opt = "--branch-" + k.replace("_", "-")
         if opt not in ap._option_string_actions:
@@ -273,11 +277,15 @@ def main(argv=None):
     ap.add_argument("--csv", default=None, help="also write the tree inventory with the branch columns as CSV")
     _inventory.add_arguments(ap)
     add_arguments(ap)
+    ap.add_argument("--wood", action="store_true", help="add the wood columns (util.wood) to the CSV")
+    from . import wood as _wood
+    _wood.add_arguments(ap)
     ap.add_argument("--terrain", action="store_true", help="measure heights from the terrain of the label-0 rows (z_ground) instead of z_low")
     _terrain.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         branch_cfg = check_params(params_of(a))
+        wood_cfg = _wood.check_params(_wood.params_of(a))
         params = _inventory.check_params(_inventory.params_of(a))
         terrain_cfg = _terrain.check_params(_terrain.params_of(a))
     except ValueError as e:
@@ -289,7 +297,7 @@ def main(argv=None):
     if data.shape[1] != 4:
         ap.error(f"--forest {a.forest}: expected N x 4 (x y z label), got {data.shape}")
     inv = _inventory.cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, branches=True, branch_cfg=branch_cfg,
-                                     **params)
+                                     wood=a.wood, wood_cfg=wood_cfg if a.wood else None, **params)
     write_skeletons(a.out, inv)
     if a.csv:
         _inventory.write_inventory(a.csv, inv)

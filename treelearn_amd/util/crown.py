@@ -1,7 +1,7 @@
 """Crown structure of a segmented forest on the device: where the crown of every tree begins, how long it is, the volume it fills, the
 ground it projects onto and its radius in eight directions.
 
-    python -m treelearn_amd.util.crown --forest labelled.npy|npz|txt|las --out crowns.npz [--csv trees.csv] [--terrain] [--branches] [--crown-layer 0.5 ...]
+    python -m treelearn_amd.util.crown --forest labelled.npy|npz|txt|las --out crowns.npz [--csv trees.csv] [--terrain] [--branches] [--wood] [--crown-layer 0.5 ...]
 
 The semantics are the project's own; tests/crown_restatement.py states them in numpy float64.  The stage runs inside
 util.inventory.tree_inventory(..., crown=True) on the label-sorted rows and the tree table that function already holds on the device.
@@ -173,10 +173,14 @@ def main(argv=None):
     ap.add_argument("--branches", action="store_true", help="add the branch columns (util.branches) to the CSV")
     from . import branches as _branches
     _branches.add_arguments(ap)
+    ap.add_argument("--wood", action="store_true", help="add the wood columns (util.wood) to the CSV (implies --branches)")
+    from . import wood as _wood
+    _wood.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         crown_cfg = check_params(params_of(a))
         branch_cfg = _branches.check_params(_branches.params_of(a))
+        wood_cfg = _wood.check_params(_wood.params_of(a))
         params = _inventory.check_params(_inventory.params_of(a))
         terrain_cfg = _terrain.check_params(_terrain.params_of(a))
     except ValueError as e:
@@ -187,8 +191,8 @@ def main(argv=None):
     data = load_forest(a.forest)
     if data.shape[1] != 4:
         ap.error(f"--forest {a.forest}: expected N x 4 (x y z label), got {data.shape}")
-    inv = _inventory.cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, crown=True, crown_cfg=crown_cfg, branches=a.branches,
-                                     branch_cfg=branch_cfg if a.branches else None, **params)
+    inv = _inventory.cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, crown=True, crown_cfg=crown_cfg, branches=a.branches or a.wood,
+                                     branch_cfg=branch_cfg if a.branches or a.wood else None, wood=a.wood, wood_cfg=wood_cfg if a.wood else None, **params)
     write_crown_profiles(a.out, inv)
     if a.csv:
         _inventory.write_inventory(a.csv, inv)

@@ -34,7 +34,10 @@ With crown=True (util.crown) the fourteen CROWN_COLUMNS follow them
 every layer of every tree and its crown radii in eight sectors: the same rows, table and reference height.
 
 With branches=True (util.branches) the thirteen BRANCH_COLUMNS follow them, and the key "skeleton" holds the node table of
-every tree's skeleton: the same rows, table and reference height."""
+every tree's skeleton: the same rows, table and reference height.
+
+With wood=True (util.wood; implies branches=True) the nine WOOD_COLUMNS follow them, and the key "cylinders" holds the fitted
+circle, the radius and the frustum of every skeleton node."""
 import argparse
 import csv
 import sys
@@ -112,7 +115,7 @@ def _device_inputs(coords, labels):
 
 def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh_max_radius=1.0, dbh_min_points=8, crown_cell=0.25,
                    offset=None, stages=None, terrain=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None, branches=False,
-                   branch_cfg=None):
+                   branch_cfg=None, wood=False, wood_cfg=None):
     """coords [N, 3] float32 or float64 (a row stride of 3 or 4 elements is read in place), labels [N] integers; numpy arrays or tensors,
     on the host or the device.  Returns a dict of numpy arrays of length T = max(label), keyed by COLUMNS (tree_id = 1..T).
     `offset` (3 values) is added to x, y, z, z_low, z_top, dbh_x, dbh_y at the end -- the un-centring of segment_forest.
@@ -124,7 +127,13 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     `crown`: True adds util.crown's CROWN_COLUMNS after them and "crown_profile", a dict of [T, L] arrays (h, n, cells) and radii [T, 8]
     (`offset` is added to crown_x, crown_y); crown_cfg holds any of util.crown's parameters.
     `branches`: True adds util.branches' BRANCH_COLUMNS after them and "skeleton", the ragged node table of every tree's skeleton
-    (`offset` is added to its xyz); branch_cfg holds any of util.branches' parameters."""
+    (`offset` is added to its xyz); branch_cfg holds any of util.branches' parameters.
+    `wood`: True implies branches=True and adds util.wood's WOOD_COLUMNS after the branch group and "cylinders", the fitted circle, radius
+    and frustum of every skeleton node (`offset` is added to its centre); wood_cfg holds any of util.wood's parameters."""
+    if wood:
+        from . import wood as _wood
+        wood_cfg = _wood.check_params(wood_cfg)                                       # before any GPU work
+        branches = True
     if branches:
         from . import branches as _branches
         branch_cfg = _branches.check_params(branch_cfg)                               # before any GPU work
@@ -204,6 +213,8 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
         *crown_dev, crown_err = _crown.crown_stage(xyz, kept_lab, T, tree, crown_cfg, mark)
     if branches:
         branch_dev = _branches.branch_stage(xyz, kept_lab, T, tree, branch_cfg, mark)
+    if wood:
+        wood_dev = _wood.wood_stage(xyz, branch_dev, T, wood_cfg, mark)
 
     table_h, counts_h, cells_h = table.cpu().numpy(), counts.cpu().numpy(), cells.cpu().numpy()
     if terrain is not None:
@@ -217,6 +228,8 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
         branch_h = {k: branch_dev[k].cpu().numpy() for k in ("kstart", "node_start", "xyz", "parent", "bin", "count")}
         branch_zref = tree[:, 2].cpu().numpy()
         branch_bad = branch_dev["err"] is not None and int(branch_dev["err"].item())
+    if wood:
+        wood_h = {k: wood_dev[k].cpu().numpy() for k in _wood.FIT_KEYS}
     bad = err is not None and int(err.item())
     mark("D2H")
     if bad:
@@ -248,6 +261,10 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
         out.update(_branches.to_columns(branch_h, branch_zref, branch_cfg, off))
         mark("branch decomposition")
         stem_keys = stem_keys + _branches.BRANCH_COLUMNS + ("skeleton",)
+    if wood:
+        out.update(_wood.to_columns(dict(out["skeleton"], xyz=branch_h["xyz"]), wood_h, branch_zref, wood_cfg, branch_cfg, off))
+        mark("wood radii")
+        stem_keys = stem_keys + _wood.WOOD_COLUMNS + ("cylinders",)
     if terrain is None:
         return {k: out[k] for k in COLUMNS + stem_keys}
     out.update({k: np.ascontiguousarray(gtable_h[:, j]) for j, k in enumerate(_GROUND_TABLE)})
@@ -259,12 +276,13 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
 
 
 def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None, branches=False,
-                    branch_cfg=None, **params):
+                    branch_cfg=None, wood=False, wood_cfg=None, **params):
     """The inventory of an N x 4 cloud (x y z label), as the command line computes it: the coordinates are centred on their float64 mean
     on the device, as segment_forest centres its input, and the mean is handed back as `offset`.  terrain=True builds the terrain of
     the label-0 rows in the same frame (util.terrain.terrain_model, parameters in terrain_cfg) and adds the GROUND_COLUMNS; stem=True
     adds util.stem's STEM_COLUMNS and "stem_profile" (parameters in stem_cfg); crown=True adds util.crown's CROWN_COLUMNS and
-    "crown_profile" (parameters in crown_cfg); branches=True adds util.branches' BRANCH_COLUMNS and "skeleton" (parameters in branch_cfg)."""
+    "crown_profile" (parameters in crown_cfg); branches=True adds util.branches' BRANCH_COLUMNS and "skeleton" (parameters in branch_cfg);
+    wood=True implies branches=True and adds util.wood's WOOD_COLUMNS and "cylinders" (parameters in wood_cfg)."""
     import torch
     pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points))
     if pts.ndim != 2 or pts.shape[1] != 4:
@@ -280,9 +298,12 @@ def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cf
         from .crown import check_params as check_crown
         crown_cfg = check_crown(crown_cfg)
     extra = {}
-    if branches:
+    if branches or wood:
         from .branches import check_params as check_branches
         extra = dict(branches=True, branch_cfg=check_branches(branch_cfg))
+    if wood:
+        from .wood import check_params as check_wood
+        extra.update(wood=True, wood_cfg=check_wood(wood_cfg))
     if not torch.cuda.is_available():
         raise RuntimeError("treelearn_amd.util.inventory runs on the GPU (tl_tree_inventory); there is no CPU fallback")
     pts = pts.to("cuda")
@@ -300,15 +321,17 @@ def write_inventory(path, inv, categories=None):
     """CSV: a header row, then one row per tree; floats as repr (they read back to the same bits), NaN as `nan`.  `categories` (per tree:
     index into segment.CATEGORIES) adds a `category` column of names.  The columns are those the dict holds: COLUMNS, and GROUND_COLUMNS
     after them when the inventory was taken with a terrain, then util.stem's STEM_COLUMNS when it was taken with stem=True, then
-    util.crown's CROWN_COLUMNS when it was taken with crown=True, then util.branches' BRANCH_COLUMNS when it was taken with branches=True
-    (each group only when the dict holds all of it)."""
+    util.crown's CROWN_COLUMNS when it was taken with crown=True, then util.branches' BRANCH_COLUMNS when it was taken with branches=True,
+    then util.wood's WOOD_COLUMNS when it was taken with wood=True (each group only when the dict holds all of it)."""
     from .branches import BRANCH_COLUMNS, BRANCH_INT_COLUMNS
     from .crown import CROWN_COLUMNS, CROWN_INT_COLUMNS
     from .stem import STEM_COLUMNS
+    from .wood import WOOD_COLUMNS, WOOD_INT_COLUMNS
     T = len(inv["tree_id"])
     columns = COLUMNS + (GROUND_COLUMNS if all(k in inv for k in GROUND_COLUMNS) else ()) + (STEM_COLUMNS if all(k in inv for k in STEM_COLUMNS) else ()) + \
-        (CROWN_COLUMNS if all(k in inv for k in CROWN_COLUMNS) else ()) + (BRANCH_COLUMNS if all(k in inv for k in BRANCH_COLUMNS) else ())
-    ints = INT_COLUMNS + ("dbh_ag_n", "stem_slices") + CROWN_INT_COLUMNS + BRANCH_INT_COLUMNS
+        (CROWN_COLUMNS if all(k in inv for k in CROWN_COLUMNS) else ()) + (BRANCH_COLUMNS if all(k in inv for k in BRANCH_COLUMNS) else ()) + \
+        (WOOD_COLUMNS if all(k in inv for k in WOOD_COLUMNS) else ())
+    ints = INT_COLUMNS + ("dbh_ag_n", "stem_slices") + CROWN_INT_COLUMNS + BRANCH_INT_COLUMNS + WOOD_INT_COLUMNS
     names = None
     if categories is not None:
         from .segment import CATEGORIES
@@ -356,6 +379,9 @@ def main(argv=None):
     ap.add_argument("--branches", action="store_true", help="add the branch columns: skeleton size and length, axis, branch count, length and order, first branch")
     from . import branches as _branches
     _branches.add_arguments(ap)
+    ap.add_argument("--wood", action="store_true", help="add the wood columns: fitted nodes, wood length, volume and area, volume of the axis and of the branches (implies --branches)")
+    from . import wood as _wood
+    _wood.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         params = check_params(params_of(a))
@@ -363,6 +389,7 @@ def main(argv=None):
         stem_cfg = _stem.check_params(_stem.params_of(a))
         crown_cfg = _crown.check_params(_crown.params_of(a))
         branch_cfg = _branches.check_params(_branches.params_of(a))
+        wood_cfg = _wood.check_params(_wood.params_of(a))
     except ValueError as e:
         ap.error(str(e))
     if not os.path.exists(a.forest):
@@ -372,8 +399,8 @@ def main(argv=None):
     if data.shape[1] != 4:
         ap.error(f"--forest {a.forest}: expected N x 4 (x y z label), got {data.shape}")
     inv = cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, stem=a.stem, stem_cfg=stem_cfg if a.stem else None,
-                          crown=a.crown, crown_cfg=crown_cfg if a.crown else None, branches=a.branches,
-                          branch_cfg=branch_cfg if a.branches else None, **params)
+                          crown=a.crown, crown_cfg=crown_cfg if a.crown else None, branches=a.branches or a.wood,
+                          branch_cfg=branch_cfg if a.branches or a.wood else None, wood=a.wood, wood_cfg=wood_cfg if a.wood else None, **params)
     write_inventory(a.out, inv)
     ok = int(np.isfinite(inv["dbh"]).sum())
     print(f"{a.forest}: {len(data)} points, {len(inv['tree_id'])} trees, {ok} with a DBH -> {a.out}")

@@ -1,7 +1,7 @@
 """Stem profiles of a segmented forest on the device: the diameter along the height of every tree (the taper curve), the stem volume, a
 diameter at breast height interpolated on the profile, the lean and the taper.
 
-    python -m treelearn_amd.util.stem --forest labelled.npy|npz|txt|las --out stems.npz [--csv trees.csv] [--terrain] [--crown] [--branches] [--stem-step 0.5 ...]
+    python -m treelearn_amd.util.stem --forest labelled.npy|npz|txt|las --out stems.npz [--csv trees.csv] [--terrain] [--crown] [--branches] [--wood] [--stem-step 0.5 ...]
 
 The semantics are the project's own; tests/stem_restatement.py states them in numpy float64.  The stage runs inside
 util.inventory.tree_inventory(..., stem=True) on the label-sorted rows and the tree table that function already holds on the device.
@@ -175,10 +175,14 @@ def main(argv=None):
     ap.add_argument("--branches", action="store_true", help="add the branch columns (util.branches) to the CSV")
     from . import branches as _branches
     _branches.add_arguments(ap)
+    ap.add_argument("--wood", action="store_true", help="add the wood columns (util.wood) to the CSV (implies --branches)")
+    from . import wood as _wood
+    _wood.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         crown_cfg = _crown.check_params(_crown.params_of(a))
         branch_cfg = _branches.check_params(_branches.params_of(a))
+        wood_cfg = _wood.check_params(_wood.params_of(a))
         stem_cfg = check_params(params_of(a))
         params = _inventory.check_params(_inventory.params_of(a))
         terrain_cfg = _terrain.check_params(_terrain.params_of(a))
@@ -191,8 +195,8 @@ def main(argv=None):
     if data.shape[1] != 4:
         ap.error(f"--forest {a.forest}: expected N x 4 (x y z label), got {data.shape}")
     inv = _inventory.cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, stem=True, stem_cfg=stem_cfg,
-                                    crown=a.crown, crown_cfg=crown_cfg if a.crown else None, branches=a.branches,
-                                    branch_cfg=branch_cfg if a.branches else None, **params)
+                                    crown=a.crown, crown_cfg=crown_cfg if a.crown else None, branches=a.branches or a.wood,
+                                    branch_cfg=branch_cfg if a.branches or a.wood else None, wood=a.wood, wood_cfg=wood_cfg if a.wood else None, **params)
     write_stem_profiles(a.out, inv)
     if a.csv:
         _inventory.write_inventory(a.csv, inv)
