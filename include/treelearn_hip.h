@@ -887,6 +887,34 @@ int tl_wood_fit(const double* sorted_xyz, int64_t m, const int64_t* perm, const 
                 const int32_t* node_parent, const int64_t* node_start, int64_t n_trees, int64_t n_nodes, const tl_wood_params* params,
                 double* radius_fit, int64_t* count, double* rmse, int32_t* state, double* centre, double* axis, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ leaf-wood separation of a labelled cloud (csrc/tl_leafwood.hip)
+ * Which rows of a tree are wood: a seed rule on the eigen-features above, then a spatial vote over the same radius neighbourhoods among
+ * the rows of the same tree.  The semantics are the project's own (restated in numpy in tests/leafwood_restatement.py).  The connectivity
+ * filter behind the vote reuses tl_skel_voxel_keys, tl_skel_nodes and tl_wood_row_nodes (util/leafwood.py).
+ * tl_leafwood_seed: one thread per row.  feats f32[n, 4] = linearity, planarity, verticality, number_of_neighbors of tl_eigen_features
+ *   (ids 5, 4, 10, 14) at `radius`.  flag u8[n] = 1 when number_of_neighbors >= min_neighbours, the three features are finite and
+ *   (linearity >= linearity_min, or planarity >= planarity_min and verticality >= verticality_min); else 0.  The f32 values are widened
+ *   to f64 and compared with the f64 thresholds; NaN gives 0.
+ * tl_leafwood_vote: one synchronous round.  xyz_sorted, sorted_keys, extent2, piece_start and n_pieces as tl_eigen_features takes them
+ *   (cells of `radius`); tag i32[n] in sorted order = (tree << 1) | flag of the round before, tree >= 0.  For a row p: a = the rows q of
+ *   the same tree with dx dx + dy dy + dz dz <= radius radius (f64, this expression, no contraction; p included), w = those of them
+ *   whose flag is 1; flag_out u8[n] = 1 exactly when 100 w >= vote_percent a, in integers; tag_out i32[n] = (tree << 1) | flag_out, the
+ *   tag of the next round (may be NULL; must not be tag).  Counts only: the same bits for any row order and any piece table.  One
+ *   wave per piece; a row whose piece is missing from the table is not written.  One launch, no atomics.
+ * A null or misaligned pointer, n or n_pieces < 0, n_pieces > n or > 2^31 - 1, extent2 outside 0 .. 2^21 - 1, tag_out == tag or a
+ * parameter outside its constraint (radius, voxel > 0 and finite; min_neighbours >= 3; the three thresholds in [0, 1]; vote_iters in
+ * 0 .. 8; vote_percent in 1 .. 100; reach 1 or 2; min_component >= 1; filter 0 or 1; NaN fails every one): TL_ERR_ARG, nothing launched.
+ * Then n = 0 (or n_pieces = 0 for tl_leafwood_vote): TL_OK without a launch, outputs untouched.  vote_iters, voxel, reach,
+ * min_component and filter are the host's (util/leafwood.py). */
+typedef struct tl_leafwood_params {
+  double radius, linearity_min, planarity_min, verticality_min, voxel;
+  int64_t min_neighbours, vote_iters, vote_percent, reach, min_component, filter;
+} tl_leafwood_params;
+int tl_leafwood_seed(const float* feats, int64_t n, const tl_leafwood_params* params, uint8_t* flag, tl_stream_t stream);
+int tl_leafwood_vote(const double* xyz_sorted, const int64_t* sorted_keys, int64_t n, const int64_t* extent2, const int64_t* piece_start,
+                     int64_t n_pieces, const int32_t* tag, const tl_leafwood_params* params, uint8_t* flag_out, int32_t* tag_out,
+                     tl_stream_t stream);
+
 /* ------------------------------------------------------------------ canopy height model of a cloud (csrc/tl_canopy.hip)
  * The per-area side of the measurements: the highest height above ground per cell (CHM) with pits and holes mended, tree tops on it,
  * and height statistics per cell of a coarser metrics grid.  The semantics are the project's own (restated in numpy float64 in

@@ -114,6 +114,11 @@ class WoodParams(_c.Structure):            # tl_wood_params
     _fields_ = [(k, _c.c_double) for k in ("max_rmse", "min_radius", "max_radius", "max_growth", "dbh_height")] + [("min_points", _i64)]
 
 
+class LeafwoodParams(_c.Structure):        # tl_leafwood_params
+    _fields_ = [(k, _c.c_double) for k in ("radius", "linearity_min", "planarity_min", "verticality_min", "voxel")] + \
+               [(k, _i64) for k in ("min_neighbours", "vote_iters", "vote_percent", "reach", "min_component", "filter")]
+
+
 _I4 = _i32 * 4
 _I3 = _i32 * 3
 
@@ -216,6 +221,8 @@ PROTOTYPES = {
                              _vp]),
     "tl_wood_row_nodes": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "tl_wood_fit": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(WoodParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tl_leafwood_seed": (_i32, [_vp, _i64, _c.POINTER(LeafwoodParams), _vp, _vp]),
+    "tl_leafwood_vote": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _c.POINTER(LeafwoodParams), _vp, _vp, _vp]),
     "tl_chm_max": (_i32, [_vp, _i32, _i64, _i64, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "tl_chm_owner": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "tl_chm_pits": (_i32, [_vp, _i32, _i32, _c.c_double, _i32, _vp, _vp, _vp, _vp]),

@@ -1,7 +1,7 @@
 """Branch structure of a segmented forest on the device: the skeleton of every tree, how long its wood is, how many branches it has, of
 which order, and where the first one leaves the stem.
 
-    python -m treelearn_amd.util.branches --forest labelled.npy|npz|txt|las --out skeletons.npz [--csv trees.csv] [--terrain] [--wood] [--branch-voxel 0.1 ...]
+    python -m treelearn_amd.util.branches --forest labelled.npy|npz|txt|las --out skeletons.npz [--csv trees.csv] [--terrain] [--wood] [--leafwood] [--branch-voxel 0.1 ...]
 
 The semantics are the project's own; tests/branches_restatement.py states them in plain Python.  The stage runs inside
 util.inventory.tree_inventory(..., branches=True) on the label-sorted rows and the tree table that function already holds on the device.
@@ -257,7 +257,7 @@ def write_skeletons(path, inv):
 
 
 def add_arguments(ap):
-    """One --branch-... option per parameter (shared with util.segment, util.inventory, util.stem, util.crown and util.wood)."""
+    """One --branch-... option per parameter (shared with util.segment, util.inventory, util.stem, util.crown, util.wood and util.leafwood)."""
     for k, v in BRANCH_DEFAULTS.items():
         opt = "--branch-" + k.replace("_", "-")
         if opt not in ap._option_string_actions:
@@ -280,12 +280,16 @@ def main(argv=None):
     ap.add_argument("--wood", action="store_true", help="add the wood columns (util.wood) to the CSV")
     from . import wood as _wood
     _wood.add_arguments(ap)
+    ap.add_argument("--leafwood", action="store_true", help="separate leaves from wood first (util.leafwood): the skeleton is that of the wood rows")
+    from . import leafwood as _leafwood
+    _leafwood.add_arguments(ap)
     ap.add_argument("--terrain", action="store_true", help="measure heights from the terrain of the label-0 rows (z_ground) instead of z_low")
     _terrain.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         branch_cfg = check_params(params_of(a))
         wood_cfg = _wood.check_params(_wood.params_of(a))
+        leafwood_cfg = _leafwood.check_params(_leafwood.params_of(a))
         params = _inventory.check_params(_inventory.params_of(a))
         terrain_cfg = _terrain.check_params(_terrain.params_of(a))
     except ValueError as e:
@@ -297,7 +301,8 @@ def main(argv=None):
     if data.shape[1] != 4:
         ap.error(f"--forest {a.forest}: expected N x 4 (x y z label), got {data.shape}")
     inv = _inventory.cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, branches=True, branch_cfg=branch_cfg,
-                                     wood=a.wood, wood_cfg=wood_cfg if a.wood else None, **params)
+                                     wood=a.wood, wood_cfg=wood_cfg if a.wood else None, leafwood=a.leafwood,
+                                     leafwood_cfg=leafwood_cfg if a.leafwood else None, **params)
     write_skeletons(a.out, inv)
     if a.csv:
         _inventory.write_inventory(a.csv, inv)

@@ -37,7 +37,10 @@ With branches=True (util.branches) the thirteen BRANCH_COLUMNS foll
 every tree's skeleton: the same rows, table and reference height.
 
 With wood=True (util.wood; implies branches=True) the nine WOOD_COLUMNS follow them, and the key "cylinders" holds the fitted
-circle, the radius and the frustum of every skeleton node."""
+circle, the radius and the frustum of every skeleton node.
+
+With leafwood=True (util.leafwood) the five LEAFWOOD_COLUMNS stand after the crown group and before the branch group, and the
+key "leafwood" holds the wood flag of every input row; with its `filter` the branch and wood stages read the wood rows only."""
 import argparse
 import csv
 import sys
@@ -115,7 +118,7 @@ def _device_inputs(coords, labels):
 
 def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh_max_radius=1.0, dbh_min_points=8, crown_cell=0.25,
                    offset=None, stages=None, terrain=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None, branches=False,
-                   branch_cfg=None, wood=False, wood_cfg=None):
+                   branch_cfg=None, wood=False, wood_cfg=None, leafwood=False, leafwood_cfg=None):
     """coords [N, 3] float32 or float64 (a row stride of 3 or 4 elements is read in place), labels [N] integers; numpy arrays or tensors,
     on the host or the device.  Returns a dict of numpy arrays of length T = max(label), keyed by COLUMNS (tree_id = 1..T).
     `offset` (3 values) is added to x, y, z, z_low, z_top, dbh_x, dbh_y at the end -- the un-centring of segment_forest.
@@ -129,7 +132,13 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     `branches`: True adds util.branches' BRANCH_COLUMNS after them and "skeleton", the ragged node table of every tree's skeleton
     (`offset` is added to its xyz); branch_cfg holds any of util.branches' parameters.
     `wood`: True implies branches=True and adds util.wood's WOOD_COLUMNS after the branch group and "cylinders", the fitted circle, radius
-    and frustum of every skeleton node (`offset` is added to its centre); wood_cfg holds any of util.wood's parameters."""
+    and frustum of every skeleton node (`offset` is added to its centre); wood_cfg holds any of util.wood's parameters.
+    `leafwood`: True adds util.leafwood's LEAFWOOD_COLUMNS after the crown group and "leafwood", a dict of wood u8 [N] (the wood flag of
+    every input row, 0 for a label < 1) and the parameters; leafwood_cfg holds any of util.leafwood's parameters.  With its `filter`
+    (the default) the branch and wood stages read the wood rows only."""
+    if leafwood:
+        from . import leafwood as _leafwood
+        leafwood_cfg = _leafwood.check_params(leafwood_cfg)                           # before any GPU work
     if wood:
         from . import wood as _wood
         wood_cfg = _wood.check_params(wood_cfg)                                       # before any GPU work
@@ -204,17 +213,26 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
         _hip.check(L.tl_crown_count(_hip.ptr(keys), m, T, _hip.ptr(cells), _hip.stream()), "tl_crown_count")
     mark("crown keys + count")
 
-    if stem or crown or branches:
+    if stem or crown or branches or leafwood:
         z_ref = gtable[:, 0] if terrain is not None else table[:, 0]
         tree = torch.stack([table[:, 3], table[:, 4], z_ref, table[:, 1]], 1).contiguous()
     if stem:
         stem_dev = _stem.stem_stage(xyz, kept_lab, T, tree, stem_cfg, mark)
     if crown:
         *crown_dev, crown_err = _crown.crown_stage(xyz, kept_lab, T, tree, crown_cfg, mark)
+    wood_xyz, wood_lab = xyz, kept_lab
+    if leafwood:
+        lw_dev = _leafwood.leafwood_stage(xyz, kept_lab, T, tree, leafwood_cfg, mark)
+        lw_rows = torch.zeros(n, dtype=torch.uint8, device=dev)
+        lw_rows[kept] = lw_dev["wood"]
+        if leafwood_cfg["filter"] and branches:                                       # the wood rows in their order, as contiguous copies
+            w = torch.nonzero(lw_dev["wood"]).reshape(-1)
+            wood_xyz, wood_lab = xyz.index_select(0, w).contiguous(), kept_lab.index_select(0, w).contiguous()
+        mark("leafwood scatter")
     if branches:
-        branch_dev = _branches.branch_stage(xyz, kept_lab, T, tree, branch_cfg, mark)
+        branch_dev = _branches.branch_stage(wood_xyz, wood_lab, T, tree, branch_cfg, mark)
     if wood:
-        wood_dev = _wood.wood_stage(xyz, branch_dev, T, wood_cfg, mark)
+        wood_dev = _wood.wood_stage(wood_xyz, branch_dev, T, wood_cfg, mark)
 
     table_h, counts_h, cells_h = table.cpu().numpy(), counts.cpu().numpy(), cells.cpu().numpy()
     if terrain is not None:
@@ -224,6 +242,10 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     if crown:
         crown_out = _crown.to_columns(*(t.cpu().numpy() for t in crown_dev), off)
         crown_bad = crown_err is not None and int(crown_err.item())
+    if leafwood:
+        lw_h = {k: lw_dev[k].cpu().numpy() for k in _leafwood.HOST_KEYS}
+        lw_rows_h, lw_zref = lw_rows.cpu().numpy(), tree[:, 2].cpu().numpy()
+        lw_bad = lw_dev["err"] is not None and int(lw_dev["err"].item())
     if branches:
         branch_h = {k: branch_dev[k].cpu().numpy() for k in ("kstart", "node_start", "xyz", "parent", "bin", "count")}
         branch_zref = tree[:, 2].cpu().numpy()
@@ -236,6 +258,9 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
         raise ValueError(f"a coordinate is not finite or lies beyond 2^20 crown cells of {p['crown_cell']} m from the origin: centre the cloud")
     if crown and crown_bad:
         raise _crown.crown_error(crown_cfg)
+    if leafwood and lw_bad:
+        from .branches import branch_error
+        raise branch_error(leafwood_cfg)
     if branches and branch_bad:
         raise _branches.branch_error(branch_cfg)
 
@@ -257,6 +282,10 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     if crown:
         out.update(crown_out)
         stem_keys = stem_keys + _crown.CROWN_COLUMNS + ("crown_profile",)
+    if leafwood:
+        out.update(_leafwood.to_columns(lw_h, lw_zref))
+        out["leafwood"] = dict(leafwood_cfg, wood=lw_rows_h)
+        stem_keys = stem_keys + _leafwood.LEAFWOOD_COLUMNS + ("leafwood",)
     if branches:
         out.update(_branches.to_columns(branch_h, branch_zref, branch_cfg, off))
         mark("branch decomposition")
@@ -276,13 +305,14 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
 
 
 def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None, branches=False,
-                    branch_cfg=None, wood=False, wood_cfg=None, **params):
+                    branch_cfg=None, wood=False, wood_cfg=None, leafwood=False, leafwood_cfg=None, **params):
     """The inventory of an N x 4 cloud (x y z label), as the command line computes it: the coordinates are centred on their float64 mean
     on the device, as segment_forest centres its input, and the mean is handed back as `offset`.  terrain=True builds the terrain of
     the label-0 rows in the same frame (util.terrain.terrain_model, parameters in terrain_cfg) and adds the GROUND_COLUMNS; stem=True
     adds util.stem's STEM_COLUMNS and "stem_profile" (parameters in stem_cfg); crown=True adds util.crown's CROWN_COLUMNS and
     "crown_profile" (parameters in crown_cfg); branches=True adds util.branches' BRANCH_COLUMNS and "skeleton" (parameters in branch_cfg);
-    wood=True implies branches=True and adds util.wood's WOOD_COLUMNS and "cylinders" (parameters in wood_cfg)."""
+    wood=True implies branches=True and adds util.wood's WOOD_COLUMNS and "cylinders" (parameters in wood_cfg); leafwood=True adds
+    util.leafwood's LEAFWOOD_COLUMNS and "leafwood" (parameters in leafwood_cfg)."""
     import torch
     pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points))
     if pts.ndim != 2 or pts.shape[1] != 4:
@@ -304,6 +334,9 @@ def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cf
     if wood:
         from .wood import check_params as check_wood
         extra.update(wood=True, wood_cfg=check_wood(wood_cfg))
+    if leafwood:
+        from .leafwood import check_params as check_leafwood
+        extra.update(leafwood=True, leafwood_cfg=check_leafwood(leafwood_cfg))
     if not torch.cuda.is_available():
         raise RuntimeError("treelearn_amd.util.inventory runs on the GPU (tl_tree_inventory); there is no CPU fallback")
     pts = pts.to("cuda")
@@ -322,16 +355,19 @@ def write_inventory(path, inv, categories=None):
     index into segment.CATEGORIES) adds a `category` column of names.  The columns are those the dict holds: COLUMNS, and GROUND_COLUMNS
     after them when the inventory was taken with a terrain, then util.stem's STEM_COLUMNS when it was taken with stem=True, then
     util.crown's CROWN_COLUMNS when it was taken with crown=True, then util.branches' BRANCH_COLUMNS when it was taken with branches=True,
-    then util.wood's WOOD_COLUMNS when it was taken with wood=True (each group only when the dict holds all of it)."""
+    then util.wood's WOOD_COLUMNS when it was taken with wood=True; util.leafwood's LEAFWOOD_COLUMNS stand between the crown and the
+    branch group when it was taken with leafwood=True (each group only when the dict holds all of it)."""
     from .branches import BRANCH_COLUMNS, BRANCH_INT_COLUMNS
     from .crown import CROWN_COLUMNS, CROWN_INT_COLUMNS
+    from .leafwood import LEAFWOOD_COLUMNS, LEAFWOOD_INT_COLUMNS
     from .stem import STEM_COLUMNS
     from .wood import WOOD_COLUMNS, WOOD_INT_COLUMNS
     T = len(inv["tree_id"])
     columns = COLUMNS + (GROUND_COLUMNS if all(k in inv for k in GROUND_COLUMNS) else ()) + (STEM_COLUMNS if all(k in inv for k in STEM_COLUMNS) else ()) + \
-        (CROWN_COLUMNS if all(k in inv for k in CROWN_COLUMNS) else ()) + (BRANCH_COLUMNS if all(k in inv for k in BRANCH_COLUMNS) else ()) + \
+        (CROWN_COLUMNS if all(k in inv for k in CROWN_COLUMNS) else ()) + (LEAFWOOD_COLUMNS if all(k in inv for k in LEAFWOOD_COLUMNS) else ()) + \
+        (BRANCH_COLUMNS if all(k in inv for k in BRANCH_COLUMNS) else ()) + \
         (WOOD_COLUMNS if all(k in inv for k in WOOD_COLUMNS) else ())
-    ints = INT_COLUMNS + ("dbh_ag_n", "stem_slices") + CROWN_INT_COLUMNS + BRANCH_INT_COLUMNS + WOOD_INT_COLUMNS
+    ints = INT_COLUMNS + ("dbh_ag_n", "stem_slices") + CROWN_INT_COLUMNS + LEAFWOOD_INT_COLUMNS + BRANCH_INT_COLUMNS + WOOD_INT_COLUMNS
     names = None
     if categories is not None:
         from .segment import CATEGORIES
@@ -382,9 +418,13 @@ def main(argv=None):
     ap.add_argument("--wood", action="store_true", help="add the wood columns: fitted nodes, wood length, volume and area, volume of the axis and of the branches (implies --branches)")
     from . import wood as _wood
     _wood.add_arguments(ap)
+    ap.add_argument("--leafwood", action="store_true", help="add the leafwood columns: wood and leaf rows, wood components, wood share, highest wood; --branches and --wood then read the wood rows only")
+    from . import leafwood as _leafwood
+    _leafwood.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         params = check_params(params_of(a))
+        leafwood_cfg = _leafwood.check_params(_leafwood.params_of(a))
         terrain_cfg = _terrain.check_params(_terrain.params_of(a))
         stem_cfg = _stem.check_params(_stem.params_of(a))
         crown_cfg = _crown.check_params(_crown.params_of(a))
@@ -400,7 +440,8 @@ def main(argv=None):
         ap.error(f"--forest {a.forest}: expected N x 4 (x y z label), got {data.shape}")
     inv = cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, stem=a.stem, stem_cfg=stem_cfg if a.stem else None,
                           crown=a.crown, crown_cfg=crown_cfg if a.crown else None, branches=a.branches or a.wood,
-                          branch_cfg=branch_cfg if a.branches or a.wood else None, wood=a.wood, wood_cfg=wood_cfg if a.wood else None, **params)
+                          branch_cfg=branch_cfg if a.branches or a.wood else None, wood=a.wood, wood_cfg=wood_cfg if a.wood else None,
+                          leafwood=a.leafwood, leafwood_cfg=leafwood_cfg if a.leafwood else None, **params)
     write_inventory(a.out, inv)
     ok = int(np.isfinite(inv["dbh"]).sum())
     print(f"{a.forest}: {len(data)} points, {len(inv['tree_id'])} trees, {ok} with a DBH -> {a.out}")

@@ -160,7 +160,7 @@ def segment_from_pointwise(coords, offset_predictions, instance_preds, shape_cfg
 def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=None, return_type="original", logger=None,
                    return_pointwise=False, inventory=False, inventory_cfg=None, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None,
                    crown=False, crown_cfg=None, canopy=False, canopy_cfg=None, branches=False, branch_cfg=None, wood=False,
-                   wood_cfg=None):
+                   wood_cfg=None, leafwood=False, leafwood_cfg=None):
     """points: N x 3 or N x 4 (x y z [label]) f64, host or device.  Returns numpy arrays: coords (f64, input frame), labels (i64),
     categories (per tree 1..T, index into CATEGORIES), and with return_pointwise the arrays of pipeline.py:100-111 (ensembled rows).
     inventory=True adds result["inventory"]: util.inventory.tree_inventory of the returned coords / labels, computed on the device in
@@ -178,7 +178,9 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
     branches=True implies inventory=True and adds util.branches' columns and result["inventory"]["skeleton"] (the node table of every
     tree's skeleton; heights from the ground with a terrain, as for the crown); branch_cfg holds any of util.branches' parameters.
     wood=True implies branches=True and adds util.wood's columns and result["inventory"]["cylinders"] (the fitted circle, radius and
-    frustum of every skeleton node); wood_cfg holds any of util.wood's parameters."""
+    frustum of every skeleton node); wood_cfg holds any of util.wood's parameters.
+    leafwood=True implies inventory=True and adds util.leafwood's columns and result["inventory"]["leafwood"] (wood u8 [N], the wood flag
+    of every row, row-aligned with coords, and the parameters); leafwood_cfg holds any of util.leafwood's parameters."""
     extra = {}
     if branches or wood:
         from .branches import check_params as check_branches
@@ -187,6 +189,10 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
     if wood:
         from .wood import check_params as check_wood
         extra.update(wood=True, wood_cfg=check_wood(wood_cfg))                        # before any GPU work
+    if leafwood:
+        from .leafwood import check_params as check_leafwood
+        extra.update(leafwood=True, leafwood_cfg=check_leafwood(leafwood_cfg))        # before any GPU work
+        inventory = True
     if canopy:
         from .canopy import canopy_model, check_params as check_canopy, stand_summary
         canopy_cfg = check_canopy(canopy_cfg)                                         # before any GPU work
@@ -324,7 +330,8 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
     tree_inventory.csv (util.inventory.write_inventory, with the category names) when the result holds an inventory; terrain.npz
     (util.terrain.write_terrain) and height_above_ground.npy when it holds a terrain; stem_profiles.npz (util.stem.write_stem_profiles) when
     the inventory holds stem profiles; crown_profiles.npz (util.crown.write_crown_profiles) when it holds crown profiles; skeletons.npz
-    (util.branches.write_skeletons) when it holds "skeleton"; cylinders.npz (util.wood.write_cylinders) when it holds "cylinders"; canopy.npz and stand.json
+    (util.branches.write_skeletons) when it holds "skeleton"; cylinders.npz (util.wood.write_cylinders) when it holds "cylinders"; leafwood.npy
+    (util.leafwood.write_leafwood) when it holds "leafwood"; canopy.npz and stand.json
     (util.canopy.write_canopy, write_stand) when the result holds a canopy."""
     save_formats = list(save_formats)
     check_formats(save_formats)
@@ -381,6 +388,9 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
         if "cylinders" in result["inventory"]:
             from .wood import write_cylinders
             write_cylinders(os.path.join(out_dir, "cylinders.npz"), result["inventory"])
+        if "leafwood" in result["inventory"]:
+            from .leafwood import write_leafwood
+            write_leafwood(os.path.join(out_dir, "leafwood.npy"), result["inventory"])
     if "terrain" in result:
         from .terrain import write_terrain
         os.makedirs(out_dir, exist_ok=True)
@@ -466,6 +476,9 @@ def parse_args(argv=None):
     ap.add_argument("--wood", action="store_true", help="write cylinders.npz and add the wood columns to tree_inventory.csv (implies --branches)")
     from . import wood as _wood
     _wood.add_arguments(ap)
+    ap.add_argument("--leafwood", action="store_true", help="write leafwood.npy (the wood flag of every row) and add the leafwood columns to tree_inventory.csv (implies --inventory); --branches and --wood then read the wood rows only")
+    from . import leafwood as _leafwood
+    _leafwood.add_arguments(ap)
     ap.add_argument("--canopy", action="store_true", help="write canopy.npz (canopy height model, tree tops, grid metrics) and stand.json (implies --terrain)")
     from . import canopy as _canopy
     _canopy.add_arguments(ap)
@@ -478,6 +491,7 @@ def parse_args(argv=None):
         _canopy.check_params(_canopy.params_of(a))
         _branches.check_params(_branches.params_of(a))
         _wood.check_params(_wood.params_of(a))
+        _leafwood.check_params(_leafwood.params_of(a))
     except ValueError as e:
         ap.error(str(e))
     check_formats(a.formats)
@@ -518,16 +532,17 @@ def main(argv=None):
                     tau_vert=a.tau_vert, tau_off=a.tau_off)
     shape = dict(SHAPE_CFG, alpha=a.alpha, buffer_size_to_determine_edge_trees=a.edge_buffer, outer_remove=a.outer_remove)
     with torch.no_grad():
-        from . import branches as _branches, canopy as _canopy, crown as _crown, stem as _stem, terrain as _terrain, wood as _wood
+        from . import branches as _branches, canopy as _canopy, crown as _crown, leafwood as _leafwood, stem as _stem, terrain as _terrain, wood as _wood
         from .inventory import params_of
         res = segment_forest(points, model, sample, grouping, shape, a.return_type, logger, return_pointwise=a.save_pointwise,
-                             inventory=a.inventory, inventory_cfg=params_of(a) if a.inventory or a.stem or a.crown or a.branches or a.wood else None,
+                             inventory=a.inventory, inventory_cfg=params_of(a) if a.inventory or a.stem or a.crown or a.branches or a.wood or a.leafwood else None,
                              terrain=a.terrain, terrain_cfg=_terrain.params_of(a) if a.terrain or a.canopy else None,
                              stem=a.stem, stem_cfg=_stem.params_of(a) if a.stem else None,
                              crown=a.crown, crown_cfg=_crown.params_of(a) if a.crown else None,
                              canopy=a.canopy, canopy_cfg=_canopy.params_of(a) if a.canopy else None,
                              branches=a.branches or a.wood, branch_cfg=_branches.params_of(a) if a.branches or a.wood else None,
-                             wood=a.wood, wood_cfg=_wood.params_of(a) if a.wood else None)
+                             wood=a.wood, wood_cfg=_wood.params_of(a) if a.wood else None,
+                             leafwood=a.leafwood, leafwood_cfg=_leafwood.params_of(a) if a.leafwood else None)
     plot_name = os.path.splitext(os.path.basename(a.forest))[0]
     save_results(res, a.out, plot_name, a.formats, save_treewise=not a.no_treewise, save_pointwise=a.save_pointwise)
     cats = np.bincount(res["categories"], minlength=3)

@@ -1,7 +1,7 @@
 """Cylinder model of a segmented forest on the device: how thick the wood of every skeleton is -- one circle fit per skeleton node, the
 radii along the branches, and the wood volume of the stem, of the branches and by branch order.
 
-    python -m treelearn_amd.util.wood --forest labelled.npy|npz|txt|las --out cylinders.npz [--csv trees.csv] [--terrain] [--wood-max-rmse 0.03 ...]
+    python -m treelearn_amd.util.wood --forest labelled.npy|npz|txt|las --out cylinders.npz [--csv trees.csv] [--terrain] [--leafwood] [--wood-max-rmse 0.03 ...]
 
 The semantics are the project's own; tests/wood_restatement.py states them in plain Python.  The stage runs inside
 util.inventory.tree_inventory(..., wood=True) behind the branch structure (util.branches, which it implies), on the same label-sorted rows.
@@ -236,11 +236,15 @@ def main(argv=None):
     _inventory.add_arguments(ap)
     _branches.add_arguments(ap)
     add_arguments(ap)
+    ap.add_argument("--leafwood", action="store_true", help="separate leaves from wood first (util.leafwood): the cylinders are those of the wood rows")
+    from . import leafwood as _leafwood
+    _leafwood.add_arguments(ap)
     ap.add_argument("--terrain", action="store_true", help="measure heights from the terrain of the label-0 rows (z_ground) instead of z_low")
     _terrain.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         wood_cfg = check_params(params_of(a))
+        leafwood_cfg = _leafwood.check_params(_leafwood.params_of(a))
         branch_cfg = _branches.check_params(_branches.params_of(a))
         params = _inventory.check_params(_inventory.params_of(a))
         terrain_cfg = _terrain.check_params(_terrain.params_of(a))
@@ -253,7 +257,7 @@ def main(argv=None):
     if data.shape[1] != 4:
         ap.error(f"--forest {a.forest}: expected N x 4 (x y z label), got {data.shape}")
     inv = _inventory.cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, branches=True, branch_cfg=branch_cfg,
-                                     wood=True, wood_cfg=wood_cfg, **params)
+                                     wood=True, wood_cfg=wood_cfg, leafwood=a.leafwood, leafwood_cfg=leafwood_cfg if a.leafwood else None, **params)
     write_cylinders(a.out, inv)
     if a.csv:
         _inventory.write_inventory(a.csv, inv)
