@@ -499,6 +499,15 @@ int tl_verticality(const double* xyz_sorted, const int64_t* sorted_keys, int64_t
 enum { TL_FEAT_COUNT = 27 };
 int tl_eigen_features(const double* xyz_sorted, const int64_t* sorted_keys, int64_t n, double radius, const int64_t* extent2,
                       const int64_t* piece_start, int64_t n_pieces, const int32_t* cols, int F, float* out, tl_stream_t stream);
+/* tl_eigen_features_scales: the same features at S radii in one launch and one walk over the candidates.  The arrays are
+ *   those of tl_eigen_features with cells of the LARGEST radius, radii[S - 1].  radii = HOST f64[S], finite, > 0, strictly ascending,
+ *   1 <= S <= TL_FEAT_MAX_SCALES.  out f32[n, S, F] in sorted order: out[i, k, :] is, bit for bit, the row i that tl_eigen_features
+ *   writes on the same sorted arrays with radius = radii[k] (every scale has its own count and sums, taken over the candidates with
+ *   squared distance <= radii[k]^2 in the order of the sorted array).  No atomics, no scratch.  TL_ERR_ARG, nothing launched: whatever
+ *   tl_eigen_features refuses, S out of range, a radius that is NaN, infinite, <= 0 or not above its predecessor. */
+#define TL_FEAT_MAX_SCALES 4
+int tl_eigen_features_scales(const double* xyz_sorted, const int64_t* sorted_keys, int64_t n, const double* radii, int S, const int64_t* extent2,
+                             const int64_t* piece_start, int64_t n_pieces, const int32_t* cols, int F, float* out, tl_stream_t stream);
 
 /* ------------------------------------------------------------------ random training crops
  * The random-crop half of SampleGenerator (tree_learn/util/data_preparation.py:136-330) on a plot resident in HBM; the
@@ -911,6 +920,13 @@ typedef struct tl_leafwood_params {
   int64_t min_neighbours, vote_iters, vote_percent, reach, min_component, filter;
 } tl_leafwood_params;
 int tl_leafwood_seed(const float* feats, int64_t n, const tl_leafwood_params* params, uint8_t* flag, tl_stream_t stream);
+/* tl_leafwood_seed_scales: the seed over S scales, one thread per row.  feats f32[n, S, 4] = the four columns of
+ *   tl_leafwood_seed as tl_eigen_features_scales writes them (16-byte aligned).  The rule of tl_leafwood_seed is applied to every
+ *   scale on its own (a scale with fewer than min_neighbours neighbours or a NaN does not hold); flag u8[n] = 1 exactly when at least
+ *   scales_min scales hold.  With S = 1 and scales_min = 1 it is tl_leafwood_seed.  TL_ERR_ARG, nothing launched: whatever
+ *   tl_leafwood_seed refuses, S outside 1 .. TL_FEAT_MAX_SCALES, scales_min outside 1 .. S.  n = 0: TL_OK without a launch. */
+int tl_leafwood_seed_scales(const float* feats, int64_t n, int S, const tl_leafwood_params* params, int scales_min, uint8_t* flag,
+                            tl_stream_t stream);
 int tl_leafwood_vote(const double* xyz_sorted, const int64_t* sorted_keys, int64_t n, const int64_t* extent2, const int64_t* piece_start,
                      int64_t n_pieces, const int32_t* tag, const tl_leafwood_params* params, uint8_t* flag_out, int32_t* tag_out,
                      tl_stream_t stream);

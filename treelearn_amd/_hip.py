@@ -186,6 +186,7 @@ PROTOTYPES = {
     "tl_group_mean": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tl_verticality": (_i32, [_vp, _vp, _i64, _c.c_double, _vp, _vp, _vp]),
     "tl_eigen_features": (_i32, [_vp, _vp, _i64, _c.c_double, _vp, _vp, _i64, _vp, _i32, _vp, _vp]),
+    "tl_eigen_features_scales": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp, _i32, _vp, _vp]),
     "tl_cluster_ws_bytes": (_i64, [_i64]),
     "tl_cluster_grid": (_i32, [_vp, _i64, _c.c_double, _vp, _vp, _vp, _vp]),
     "tl_hdbscan_ws_bytes": (_i64, [_i64]),
@@ -222,6 +223,7 @@ PROTOTYPES = {
     "tl_wood_row_nodes": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
     "tl_wood_fit": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _c.POINTER(WoodParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tl_leafwood_seed": (_i32, [_vp, _i64, _c.POINTER(LeafwoodParams), _vp, _vp]),
+    "tl_leafwood_seed_scales": (_i32, [_vp, _i64, _i32, _c.POINTER(LeafwoodParams), _i32, _vp, _vp]),
     "tl_leafwood_vote": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _c.POINTER(LeafwoodParams), _vp, _vp, _vp]),
     "tl_chm_max": (_i32, [_vp, _i32, _i64, _i64, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "tl_chm_owner": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -18,6 +18,11 @@
 // Per point: sample covariance (n - 1), all three eigenpairs by cyclic Jacobi in f64, l1 >= l2 >= l3 clamped at 0, every
 // eigenvector oriented by z >= 0 (then y >= 0, then x >= 0).  Fewer than 3 neighbours: NaN in every column but
 // number_of_neighbors.  Only the requested columns are computed and stored.
+//
+// tl_eigen_features_scales: the same at 1 to 4 ascending radii in one launch.  The cells are those of the largest radius;
+// one walk over the staged candidates feeds a count and nine sums per scale (k_eigen_features_scales<S>, accumulators in registers).
+// Every scale's row is, bit for bit, the row of tl_eigen_features on the same sorted arrays at that radius.  The covariance, eigen3 and
+// the column switch exist once (feature_row) for both kernels.
 #include "tl_common.h"
 
 #pragma clang fp contract(off)
@@ -83,6 +88,50 @@ __device__ void eigen3(double a00, double a01, double a02, double a11, double a1
     const bool flip = z < 0.0 || (z == 0.0 && (y < 0.0 || (y == 0.0 && x < 0.0)));
     if (flip) { x = -x; y = -y; z = -z; }
     vec[k][0] = x; vec[k][1] = y; vec[k][2] = z;
+  }
+}
+
+// One output row from the neighbourhood sums of one point at one radius: the covariance, eigen3 and the column switch.  The one copy
+// that k_eigen_features and k_eigen_features_scales share.
+__device__ __forceinline__ void feature_row(int64_t cnt, double s0, double s1, double s2, double s00, double s01, double s02, double s11,
+                                            double s12, double s22, const FeatCols& cols, float* __restrict__ o) {
+  if (cnt < 3) {
+    for (int c = 0; c < cols.F; ++c) o[c] = cols.id[c] == kNumberOfNeighbors ? (float)cnt : __builtin_nanf("");
+    return;
+  }
+  const double inv_n = 1.0 / (double)cnt, inv = 1.0 / (double)(cnt - 1);
+  double l[3], e[3][3];
+  eigen3((s00 - s0 * s0 * inv_n) * inv, (s01 - s0 * s1 * inv_n) * inv, (s02 - s0 * s2 * inv_n) * inv,
+         (s11 - s1 * s1 * inv_n) * inv, (s12 - s1 * s2 * inv_n) * inv, (s22 - s2 * s2 * inv_n) * inv, l, e);
+  const double l1 = l[0], l2 = l[1], l3 = l[2], s = l1 + l2 + l3;
+  for (int c = 0; c < cols.F; ++c) {
+    double v;
+    switch (cols.id[c]) {
+      case kEigenvalueSum: v = s; break;
+      case kOmnivariance: v = cbrt(l1 * l2 * l3); break;
+      case kEigenentropy: v = -(xlnx(l1) + xlnx(l2) + xlnx(l3)); break;
+      case kAnisotropy: v = (l1 - l3) / l1; break;
+      case kPlanarity: v = (l2 - l3) / l1; break;
+      case kLinearity: v = (l1 - l2) / l1; break;
+      case kPCA1: v = l1 / s; break;
+      case kPCA2: v = l2 / s; break;
+      case kSurfaceVariation: v = l3 / s; break;
+      case kSphericity: v = l3 / l1; break;
+      case kVerticality: v = 1.0 - fabs(e[2][2]); break;
+      case kNx: v = e[2][0]; break;
+      case kNy: v = e[2][1]; break;
+      case kNz: v = e[2][2]; break;
+      case kNumberOfNeighbors: v = (double)cnt; break;
+      case kEigenvalue1: v = l1; break;
+      case kEigenvalue2: v = l2; break;
+      case kEigenvalue3: v = l3; break;
+      default: {
+        const int k = cols.id[c] - kEigenvector1x;                 // 0..8, checked by the launcher
+        const int a = k / 3, d = k - 3 * a;
+        v = a == 0 ? pick3(e[0], d) : (a == 1 ? pick3(e[1], d) : pick3(e[2], d));
+      }
+    }
+    o[c] = (float)v;
   }
 }
 
@@ -156,45 +205,104 @@ __global__ void __launch_bounds__(64) k_eigen_features(const double* __restrict_
   }
   if (!valid) return;
 
-  float* __restrict__ o = out + i * (int64_t)cols.F;
-  if (cnt < 3) {
-    for (int c = 0; c < cols.F; ++c) o[c] = cols.id[c] == kNumberOfNeighbors ? (float)cnt : __builtin_nanf("");
-    return;
+  feature_row(cnt, s0, s1, s2, s00, s01, s02, s11, s12, s22, cols, out + i * (int64_t)cols.F);
+}
+
+// S radii in one walk.  The cells are those of the LARGEST radius, so the 9 ranges hold every candidate of every scale; the
+// work split, the staging and the order of the additions are those of k_eigen_features.  Scale k keeps its own count and nine sums and
+// takes a candidate when the same d^2 <= r_k^2: its row is, bit for bit, what k_eigen_features gives on the same sorted arrays with
+// radius r_k.  The accumulators are indexed by the unrolled k only (registers, no scratch).
+struct FeatRadii2 { double v[TL_FEAT_MAX_SCALES]; };
+struct FeatSums { double s0, s1, s2, s00, s01, s02, s11, s12, s22; int64_t cnt; };
+
+template <int S>
+__global__ void __launch_bounds__(64) k_eigen_features_scales(const double* __restrict__ xyz, const int64_t* __restrict__ keys, int64_t n,
+                                                              FeatRadii2 r2, int64_t nx, int64_t ny, const int64_t* __restrict__ piece_start,
+                                                              int64_t n_pieces, FeatCols cols, float* __restrict__ out) {
+  __shared__ double buf[2][kChunk * 3];
+  __shared__ int64_t rng[18];                       // [r][lo, hi) of the 9 (dx, dy) columns, x-major
+  const int lane = threadIdx.x;
+  const int64_t w = blockIdx.x;
+  if (w >= n_pieces) return;
+  const int64_t start = piece_start[w];
+  if (start < 0 || start >= n) return;              // (uniform: nothing in a table can send the wave out of the arrays)
+  const int64_t key = keys[start], col = key >> kBits;
+  const int64_t cx = key >> (2 * kBits), cy = (key >> kBits) & kMask;
+  const int64_t blk_end = ((start >> 6) + 1) << 6 < n ? ((start >> 6) + 1) << 6 : n;     // a piece stays inside its aligned 64-block
+  const int64_t i = start + lane;
+  const bool valid = i < blk_end && (keys[i < blk_end ? i : start] >> kBits) == col;       // (a prefix of the lanes: the array is sorted)
+  const int nvalid = __popcll(__ballot(valid));
+  if (lane < 18) {
+    const int r = lane >> 1;
+    const int64_t x = cx - 1 + r / 3, y = cy - 1 + r % 3;
+    const int64_t zmin = key & kMask, zmax = keys[start + nvalid - 1] & kMask;
+    const int64_t z0 = zmin > 0 ? zmin - 1 : 0, z1 = zmax < kMask ? zmax + 1 : kMask;
+    int64_t v = 0;                                  // a column outside the plot: the empty range [0, 0)
+    if (x >= 0 && x <= nx && y >= 0 && y <= ny) {
+      const int64_t kb = (x << (2 * kBits)) | (y << kBits);
+      v = lower_bound(keys, n, (lane & 1) ? (kb | z1) + 1 : (kb | z0));
+    }
+    rng[lane] = v;
   }
-  const double inv_n = 1.0 / (double)cnt, inv = 1.0 / (double)(cnt - 1);
-  double l[3], e[3][3];
-  eigen3((s00 - s0 * s0 * inv_n) * inv, (s01 - s0 * s1 * inv_n) * inv, (s02 - s0 * s2 * inv_n) * inv,
-         (s11 - s1 * s1 * inv_n) * inv, (s12 - s1 * s2 * inv_n) * inv, (s22 - s2 * s2 * inv_n) * inv, l, e);
-  const double l1 = l[0], l2 = l[1], l3 = l[2], s = l1 + l2 + l3;
-  for (int c = 0; c < cols.F; ++c) {
-    double v;
-    switch (cols.id[c]) {
-      case kEigenvalueSum: v = s; break;
-      case kOmnivariance: v = cbrt(l1 * l2 * l3); break;
-      case kEigenentropy: v = -(xlnx(l1) + xlnx(l2) + xlnx(l3)); break;
-      case kAnisotropy: v = (l1 - l3) / l1; break;
-      case kPlanarity: v = (l2 - l3) / l1; break;
-      case kLinearity: v = (l1 - l2) / l1; break;
-      case kPCA1: v = l1 / s; break;
-      case kPCA2: v = l2 / s; break;
-      case kSurfaceVariation: v = l3 / s; break;
-      case kSphericity: v = l3 / l1; break;
-      case kVerticality: v = 1.0 - fabs(e[2][2]); break;
-      case kNx: v = e[2][0]; break;
-      case kNy: v = e[2][1]; break;
-      case kNz: v = e[2][2]; break;
-      case kNumberOfNeighbors: v = (double)cnt; break;
-      case kEigenvalue1: v = l1; break;
-      case kEigenvalue2: v = l2; break;
-      case kEigenvalue3: v = l3; break;
-      default: {
-        const int k = cols.id[c] - kEigenvector1x;                 // 0..8, checked by the launcher
-        const int a = k / 3, d = k - 3 * a;
-        v = a == 0 ? pick3(e[0], d) : (a == 1 ? pick3(e[1], d) : pick3(e[2], d));
+  __syncthreads();
+  const int64_t ip = valid ? i : start;
+  const double px = xyz[ip * 3], py = xyz[ip * 3 + 1], pz = xyz[ip * 3 + 2];
+
+  // the chunks of the 9 ranges, in order
+  int r = -1; int64_t off = 0, hi = 0;
+  auto next = [&](int64_t& c_off, int& c_cnt) -> bool {
+    while (off >= hi) { if (++r >= 9) return false; off = rng[2 * r]; hi = rng[2 * r + 1]; }
+    c_off = off; c_cnt = (int)((hi - off) < (int64_t)kChunk ? (hi - off) : (int64_t)kChunk); off += c_cnt;
+    return true;
+  };
+  double reg[kLoads];
+  auto fetch = [&](int64_t c_off, int c_cnt) {
+    const double* __restrict__ src = xyz + c_off * 3;
+#pragma unroll
+    for (int k = 0; k < kLoads; ++k) { const int idx = k * 64 + lane; reg[k] = idx < c_cnt * 3 ? src[idx] : 0.0; }
+  };
+
+  FeatSums a[S];
+#pragma unroll
+  for (int k = 0; k < S; ++k) a[k] = FeatSums{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int64_t c_off = 0; int c_cnt = 0, b = 0;
+  bool have = next(c_off, c_cnt);
+  if (have) fetch(c_off, c_cnt);
+  while (have) {
+    double* cur = buf[b];
+#pragma unroll
+    for (int k = 0; k < kLoads; ++k) cur[k * 64 + lane] = reg[k];
+    __syncthreads();
+    const int m = c_cnt;
+    have = next(c_off, c_cnt);
+    if (have) fetch(c_off, c_cnt);                  // in flight while the lanes walk the current chunk
+    for (int j = 0; j < m; ++j) {
+      const double dx = cur[3 * j] - px, dy = cur[3 * j + 1] - py, dz = cur[3 * j + 2] - pz;
+      const double d2 = dx * dx + dy * dy + dz * dz;
+      if (d2 <= r2.v[S - 1]) {                      // (the radii ascend: outside the largest is outside all)
+        const double xx = dx * dx, xy = dx * dy, xz = dx * dz, yy = dy * dy, yz = dy * dz, zz = dz * dz;
+#pragma unroll
+        for (int k = 0; k < S; ++k)
+          if (d2 <= r2.v[k]) {
+            ++a[k].cnt; a[k].s0 += dx; a[k].s1 += dy; a[k].s2 += dz;
+            a[k].s00 += xx; a[k].s01 += xy; a[k].s02 += xz; a[k].s11 += yy; a[k].s12 += yz; a[k].s22 += zz;
+          }
       }
     }
-    o[c] = (float)v;
+    b ^= 1;
   }
+  if (!valid) return;
+
+#pragma unroll
+  for (int k = 0; k < S; ++k)
+    feature_row(a[k].cnt, a[k].s0, a[k].s1, a[k].s2, a[k].s00, a[k].s01, a[k].s02, a[k].s11, a[k].s12, a[k].s22, cols,
+                out + (i * S + k) * (int64_t)cols.F);
+}
+
+template <int S>
+void launch_scales(const double* xyz, const int64_t* keys, int64_t n, const FeatRadii2& r2, const int64_t* extent2, const int64_t* piece_start,
+                   int64_t n_pieces, const FeatCols& fc, float* out, tl_stream_t stream) {
+  k_eigen_features_scales<S><<<(unsigned)n_pieces, 64, 0, tl_s(stream)>>>(xyz, keys, n, r2, extent2[0], extent2[1], piece_start, n_pieces, fc, out);
 }
 
 }  // namespace
@@ -214,6 +322,33 @@ int tl_eigen_features(const double* xyz_sorted, const int64_t* sorted_keys, int6
   }
   k_eigen_features<<<(unsigned)n_pieces, 64, 0, tl_s(stream)>>>(xyz_sorted, sorted_keys, n, radius * radius, extent2[0], extent2[1],
                                                                 piece_start, n_pieces, fc, out);
+  TL_CHECK_LAUNCH();
+  return TL_OK;
+}
+
+int tl_eigen_features_scales(const double* xyz_sorted, const int64_t* sorted_keys, int64_t n, const double* radii, int S, const int64_t* extent2,
+                             const int64_t* piece_start, int64_t n_pieces, const int32_t* cols, int F, float* out, tl_stream_t stream) {
+  if (!xyz_sorted || !sorted_keys || !radii || !extent2 || !piece_start || !cols || !out || n <= 0 || n_pieces <= 0) return TL_ERR_ARG;
+  if (S < 1 || S > TL_FEAT_MAX_SCALES || F < 1 || F > TL_FEAT_COUNT || n_pieces > n || n_pieces > 0x7fffffffll) return TL_ERR_ARG;
+  if (extent2[0] < 0 || extent2[0] > kMask || extent2[1] < 0 || extent2[1] > kMask) return TL_ERR_ARG;
+  FeatRadii2 r2;
+  for (int k = 0; k < TL_FEAT_MAX_SCALES; ++k) {
+    const double r = radii[k < S ? k : S - 1];
+    if (!(r > 0.0 && r < __builtin_inf()) || (k > 0 && k < S && !(r > radii[k - 1]))) return TL_ERR_ARG;      // (NaN fails)
+    r2.v[k] = r * r;
+  }
+  FeatCols fc;
+  fc.F = F;
+  for (int c = 0; c < TL_FEAT_COUNT; ++c) {
+    fc.id[c] = c < F ? cols[c] : 0;
+    if (c < F && (cols[c] < 0 || cols[c] >= TL_FEAT_COUNT)) return TL_ERR_ARG;
+  }
+  switch (S) {
+    case 1: launch_scales<1>(xyz_sorted, sorted_keys, n, r2, extent2, piece_start, n_pieces, fc, out, stream); break;
+    case 2: launch_scales<2>(xyz_sorted, sorted_keys, n, r2, extent2, piece_start, n_pieces, fc, out, stream); break;
+    case 3: launch_scales<3>(xyz_sorted, sorted_keys, n, r2, extent2, piece_start, n_pieces, fc, out, stream); break;
+    default: launch_scales<4>(xyz_sorted, sorted_keys, n, r2, extent2, piece_start, n_pieces, fc, out, stream); break;
+  }
   TL_CHECK_LAUNCH();
   return TL_OK;
 }

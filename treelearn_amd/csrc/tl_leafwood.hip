@@ -3,6 +3,7 @@
 // over the same radius neighbourhoods.  The connectivity filter behind the vote is the caller's, on tl_skel_voxel_keys / tl_skel_nodes.
 //
 // tl_leafwood_seed: one thread per row, four f32 features in, one byte out.
+// tl_leafwood_seed_scales: the same rule at each of S scales (the rows of tl_eigen_features_scales), counted against scales_min (§26).
 // tl_leafwood_vote: the work split of k_eigen_features (tl_features.hip): points sorted by a (radius)-sized cell key with z fastest, one
 // wave per PIECE (up to 64 consecutive points of one (x, y) column of cells inside one aligned 64-block), one point per lane.  Lanes
 // 0..17 find the ends of the 9 candidate ranges by binary search, once per piece; the ranges are staged through LDS in chunks of kChunk
@@ -36,6 +37,23 @@ __global__ void __launch_bounds__(kBlock) k_leafwood_seed(const float* __restric
     const bool finite = fabs(lin) < inf && fabs(pla) < inf && fabs(ver) < inf;                    // (NaN fails)
     const bool limb = lin >= a.linearity_min, patch = pla >= a.planarity_min && ver >= a.verticality_min;
     flag[j] = (nn >= (double)a.min_neighbours && finite && (limb || patch)) ? 1 : 0;
+  }
+}
+
+// The seed rule at S scales: feats f32 [n, S, 4]; the rule above per scale, the flag is 1 when at least scales_min hold.
+__global__ void __launch_bounds__(kBlock) k_leafwood_seed_scales(const float* __restrict__ feats, int64_t n, int S, tl_leafwood_params a,
+                                                                 int scales_min, uint8_t* __restrict__ flag) {
+  const double inf = __builtin_inf();
+  for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += (int64_t)gridDim.x * kBlock) {
+    int hold = 0;
+    for (int k = 0; k < S; ++k) {
+      const float4 f = reinterpret_cast<const float4*>(feats)[j * S + k];
+      const double lin = (double)f.x, pla = (double)f.y, ver = (double)f.z, nn = (double)f.w;
+      const bool finite = fabs(lin) < inf && fabs(pla) < inf && fabs(ver) < inf;                  // (NaN fails)
+      const bool limb = lin >= a.linearity_min, patch = pla >= a.planarity_min && ver >= a.verticality_min;
+      hold += (nn >= (double)a.min_neighbours && finite && (limb || patch)) ? 1 : 0;
+    }
+    flag[j] = hold >= scales_min ? 1 : 0;
   }
 }
 
@@ -151,6 +169,17 @@ int tl_leafwood_seed(const float* feats, int64_t n, const tl_leafwood_params* pa
   if (!params_ok(params)) return TL_ERR_ARG;
   if (n == 0) return TL_OK;
   k_leafwood_seed<<<tl_grid(n, kBlock), kBlock, 0, tl_s(stream)>>>(feats, n, *params, flag);
+  TL_CHECK_LAUNCH();
+  return TL_OK;
+}
+
+int tl_leafwood_seed_scales(const float* feats, int64_t n, int S, const tl_leafwood_params* params, int scales_min, uint8_t* flag,
+                            tl_stream_t stream) {
+  if (!feats || !flag || n < 0 || !aligned(feats, 16)) return TL_ERR_ARG;
+  if (S < 1 || S > TL_FEAT_MAX_SCALES || scales_min < 1 || scales_min > S) return TL_ERR_ARG;
+  if (!params_ok(params)) return TL_ERR_ARG;
+  if (n == 0) return TL_OK;
+  k_leafwood_seed_scales<<<tl_grid(n, kBlock), kBlock, 0, tl_s(stream)>>>(feats, n, S, *params, scales_min, flag);
   TL_CHECK_LAUNCH();
   return TL_OK;
 }

@@ -290,6 +290,7 @@ def main(argv=None):
         branch_cfg = check_params(params_of(a))
         wood_cfg = _wood.check_params(_wood.params_of(a))
         leafwood_cfg = _leafwood.check_params(_leafwood.params_of(a))
+        lw_scales = _leafwood.check_scales(_leafwood.scales_of(a))
         params = _inventory.check_params(_inventory.params_of(a))
         terrain_cfg = _terrain.check_params(_terrain.params_of(a))
     except ValueError as e:
@@ -302,7 +303,8 @@ def main(argv=None):
         ap.error(f"--forest {a.forest}: expected N x 4 (x y z label), got {data.shape}")
     inv = _inventory.cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, branches=True, branch_cfg=branch_cfg,
                                      wood=a.wood, wood_cfg=wood_cfg if a.wood else None, leafwood=a.leafwood,
-                                     leafwood_cfg=leafwood_cfg if a.leafwood else None, **params)
+                                     leafwood_cfg=leafwood_cfg if a.leafwood else None,
+                                     leafwood_scales=lw_scales["scales"], leafwood_scales_min=lw_scales["scales_min"], **params)
     write_skeletons(a.out, inv)
     if a.csv:
         _inventory.write_inventory(a.csv, inv)

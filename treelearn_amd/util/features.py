@@ -1,6 +1,10 @@
 """Geometric point features: the full eigen-feature set of the radius neighbourhood.
 
     python -m treelearn_amd.util.features --forest cloud.npy --out features.npz --features linearity planarity verticality [--radius 0.6] [--voxel-size 0.1]
+    python -m treelearn_amd.util.features --forest cloud.npy --out features.npz --features linearity planarity --radii 0.2 0.4 0.6
+
+With --radii (1 to 4 ascending radii) the file holds features f32 [M, S, F] of all radii, from one cell sort and one launch of
+tl_eigen_features_scales (util.prepare.compute_features_scales), and `radii` beside `feature_names` and `points`.
 
 The reference's `compute_features(points, search_radius, feature_names=[...])` (tree_learn/util/data_preparation.py:82-88) forwards any
 list of jakteristics feature names; `util.prepare.compute_features` does the same through `tl_eigen_features` (csrc/tl_features.hip).
@@ -63,6 +67,25 @@ def feature_ids(feature_names):
     return [FEATURE_NAMES.index(n) for n in check_feature_names(feature_names)]
 
 
+MAX_SCALES = 4                                                                         # TL_FEAT_MAX_SCALES
+
+
+def check_radii(radii):
+    """1 .. MAX_SCALES finite radii > 0 in strictly ascending order as a list of float, or ValueError.  Touches no GPU."""
+    if isinstance(radii, (str, bytes)) or not hasattr(radii, "__iter__"):
+        raise ValueError(f"radii must be a sequence of numbers, got {radii!r}")
+    vals = list(radii)
+    if not 1 <= len(vals) <= MAX_SCALES:
+        raise ValueError(f"radii must hold 1 to {MAX_SCALES} values, got {len(vals)}")
+    for v in vals:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not v > 0:
+            raise ValueError(f"every radius must be a finite number > 0, got {v!r}")
+    vals = [float(v) for v in vals]
+    if any(b <= a for a, b in zip(vals, vals[1:])):
+        raise ValueError(f"radii must be strictly ascending, got {vals}")
+    return vals
+
+
 # ------------------------------------------------------------------------------------------------ the cache file features/<plot>.npz
 def save_feature_cache(path, feats, feature_names):
     """With the default list the file holds `features` only (the bytes it always had); with another list also `feature_names`."""
@@ -91,11 +114,16 @@ def parse_args(argv=None):
     ap.add_argument("--forest", required=True, help="input cloud: .npy / .npz / .txt / .las, N x 3 or N x 4")
     ap.add_argument("--out", required=True, help="output .npz: features f32 [M, F], feature_names, points f64 [M, 3]")
     ap.add_argument("--features", nargs="+", required=True, help="any of: " + " ".join(FEATURE_NAMES))
-    ap.add_argument("--radius", type=float, default=0.6, help="search radius in metres")
+    rad = ap.add_mutually_exclusive_group()
+    rad.add_argument("--radius", type=float, default=0.6, help="search radius in metres")
+    rad.add_argument("--radii", type=float, nargs="+", default=None, metavar="R",
+                     help="1 to 4 ascending search radii: features [M, S, F] of all of them from one launch, and `radii` in the output")
     ap.add_argument("--voxel-size", type=float, default=0.1, help="down-sample to this voxel size first; 0 takes the cloud as it is")
     a = ap.parse_args(argv)
     try:
         a.features = check_feature_names(a.features)
+        if a.radii is not None:
+            a.radii = check_radii(a.radii)
     except ValueError as e:
         ap.error(str(e))
     if not a.radius > 0:
@@ -111,12 +139,17 @@ def parse_args(argv=None):
 
 def main(argv=None):
     a = parse_args(argv)
-    from .prepare import compute_features, voxelize
+    from .prepare import compute_features, compute_features_scales, voxelize
     from .segment import load_forest
     pts = np.ascontiguousarray(load_forest(a.forest)[:, :3], dtype=np.float64)
     if a.voxel_size > 0:
         vox, _ = voxelize(pts, a.voxel_size)
         pts = vox[:, :3].cpu().numpy().astype(np.float64)
+    if a.radii is not None:
+        feats = compute_features_scales(pts, a.radii, a.features)
+        np.savez_compressed(a.out, features=feats.cpu().numpy(), radii=np.array(a.radii, np.float64), feature_names=np.array(a.features), points=pts)
+        print(f"{len(pts)} points x {len(a.radii)} radii x {len(a.features)} features -> {a.out}")
+        return 0
     feats = compute_features(pts, search_radius=a.radius, feature_names=a.features)
     np.savez_compressed(a.out, features=feats.cpu().numpy(), feature_names=np.array(a.features), points=pts)
     print(f"{len(pts)} points x {len(a.features)} features -> {a.out}")

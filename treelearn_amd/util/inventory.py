@@ -118,7 +118,8 @@ def _device_inputs(coords, labels):
 
 def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh_max_radius=1.0, dbh_min_points=8, crown_cell=0.25,
                    offset=None, stages=None, terrain=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None, branches=False,
-                   branch_cfg=None, wood=False, wood_cfg=None, leafwood=False, leafwood_cfg=None):
+                   branch_cfg=None, wood=False, wood_cfg=None, leafwood=False, leafwood_cfg=None, leafwood_scales=None,
+                   leafwood_scales_min=None):
     """coords [N, 3] float32 or float64 (a row stride of 3 or 4 elements is read in place), labels [N] integers; numpy arrays or tensors,
     on the host or the device.  Returns a dict of numpy arrays of length T = max(label), keyed by COLUMNS (tree_id = 1..T).
     `offset` (3 values) is added to x, y, z, z_low, z_top, dbh_x, dbh_y at the end -- the un-centring of segment_forest.
@@ -134,11 +135,14 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     `wood`: True implies branches=True and adds util.wood's WOOD_COLUMNS after the branch group and "cylinders", the fitted circle, radius
     and frustum of every skeleton node (`offset` is added to its centre); wood_cfg holds any of util.wood's parameters.
     `leafwood`: True adds util.leafwood's LEAFWOOD_COLUMNS after the crown group and "leafwood", a dict of wood u8 [N] (the wood flag of
-    every input row, 0 for a label < 1) and the parameters; leafwood_cfg holds any of util.leafwood's parameters.  With its `filter`
+    every input row, 0 for a label < 1) and the parameters; leafwood_cfg holds any of util.leafwood's parameters; leafwood_scales (1 to 4
+    ascending radii) and leafwood_scales_min make the seed a count over scales (util.leafwood.check_scales) and are recorded
+    in that dict.  With its `filter`
     (the default) the branch and wood stages read the wood rows only."""
     if leafwood:
         from . import leafwood as _leafwood
         leafwood_cfg = _leafwood.check_params(leafwood_cfg)                           # before any GPU work
+        lw_scales = _leafwood.check_scales(scales=leafwood_scales, scales_min=leafwood_scales_min)
     if wood:
         from . import wood as _wood
         wood_cfg = _wood.check_params(wood_cfg)                                       # before any GPU work
@@ -222,7 +226,7 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
         *crown_dev, crown_err = _crown.crown_stage(xyz, kept_lab, T, tree, crown_cfg, mark)
     wood_xyz, wood_lab = xyz, kept_lab
     if leafwood:
-        lw_dev = _leafwood.leafwood_stage(xyz, kept_lab, T, tree, leafwood_cfg, mark)
+        lw_dev = _leafwood.leafwood_stage(xyz, kept_lab, T, tree, leafwood_cfg, mark, scales=lw_scales if lw_scales["scales"] is not None else None)
         lw_rows = torch.zeros(n, dtype=torch.uint8, device=dev)
         lw_rows[kept] = lw_dev["wood"]
         if leafwood_cfg["filter"] and branches:                                       # the wood rows in their order, as contiguous copies
@@ -284,7 +288,7 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
         stem_keys = stem_keys + _crown.CROWN_COLUMNS + ("crown_profile",)
     if leafwood:
         out.update(_leafwood.to_columns(lw_h, lw_zref))
-        out["leafwood"] = dict(leafwood_cfg, wood=lw_rows_h)
+        out["leafwood"] = dict(leafwood_cfg, wood=lw_rows_h, **(lw_scales if lw_scales["scales"] is not None else {}))
         stem_keys = stem_keys + _leafwood.LEAFWOOD_COLUMNS + ("leafwood",)
     if branches:
         out.update(_branches.to_columns(branch_h, branch_zref, branch_cfg, off))
@@ -305,7 +309,8 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
 
 
 def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None, branches=False,
-                    branch_cfg=None, wood=False, wood_cfg=None, leafwood=False, leafwood_cfg=None, **params):
+                    branch_cfg=None, wood=False, wood_cfg=None, leafwood=False, leafwood_cfg=None, leafwood_scales=None,
+                    leafwood_scales_min=None, **params):
     """The inventory of an N x 4 cloud (x y z label), as the command line computes it: the coordinates are centred on their float64 mean
     on the device, as segment_forest centres its input, and the mean is handed back as `offset`.  terrain=True builds the terrain of
     the label-0 rows in the same frame (util.terrain.terrain_model, parameters in terrain_cfg) and adds the GROUND_COLUMNS; stem=True
@@ -335,8 +340,9 @@ def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cf
         from .wood import check_params as check_wood
         extra.update(wood=True, wood_cfg=check_wood(wood_cfg))
     if leafwood:
-        from .leafwood import check_params as check_leafwood
-        extra.update(leafwood=True, leafwood_cfg=check_leafwood(leafwood_cfg))
+        from .leafwood import check_params as check_leafwood, check_scales
+        extra.update(leafwood=True, leafwood_cfg=check_leafwood(leafwood_cfg), leafwood_scales=leafwood_scales, leafwood_scales_min=leafwood_scales_min)
+        check_scales(scales=leafwood_scales, scales_min=leafwood_scales_min)
     if not torch.cuda.is_available():
         raise RuntimeError("treelearn_amd.util.inventory runs on the GPU (tl_tree_inventory); there is no CPU fallback")
     pts = pts.to("cuda")
@@ -425,6 +431,7 @@ def main(argv=None):
     try:
         params = check_params(params_of(a))
         leafwood_cfg = _leafwood.check_params(_leafwood.params_of(a))
+        lw_scales = _leafwood.check_scales(_leafwood.scales_of(a))
         terrain_cfg = _terrain.check_params(_terrain.params_of(a))
         stem_cfg = _stem.check_params(_stem.params_of(a))
         crown_cfg = _crown.check_params(_crown.params_of(a))
@@ -441,7 +448,8 @@ def main(argv=None):
     inv = cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, stem=a.stem, stem_cfg=stem_cfg if a.stem else None,
                           crown=a.crown, crown_cfg=crown_cfg if a.crown else None, branches=a.branches or a.wood,
                           branch_cfg=branch_cfg if a.branches or a.wood else None, wood=a.wood, wood_cfg=wood_cfg if a.wood else None,
-                          leafwood=a.leafwood, leafwood_cfg=leafwood_cfg if a.leafwood else None, **params)
+                          leafwood=a.leafwood, leafwood_cfg=leafwood_cfg if a.leafwood else None,
+                          leafwood_scales=lw_scales["scales"], leafwood_scales_min=lw_scales["scales_min"], **params)
     write_inventory(a.out, inv)
     ok = int(np.isfinite(inv["dbh"]).sum())
     print(f"{a.forest}: {len(data)} points, {len(inv['tree_id'])} trees, {ok} with a DBH -> {a.out}")

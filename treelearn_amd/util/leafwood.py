@@ -24,7 +24,13 @@ behind the crown stage and in front of util.branches.  All rules are per gathere
   filter    True: util.branches and util.wood read the wood rows only (the tree table stays that of all rows; the stem and crown stages
             are untouched: a crown is its leaves).  False: their outputs are the bits of a call without leafwood.
 
-Known limits: the seed is one scale; conifer needles along a twig are linear like the twig; a stem patch scanned from one side at long
+  scales    (tests/leafwood_scales_restatement.py) `scales` = 1 to 4 ascending radii and `scales_min`, beside the eleven parameters
+            (check_scales; --leafwood-scales R [R ...] --leafwood-scales-min K): the features at every scale from one sorted_cells at
+            max(scales) and one tl_eigen_features_scales; the seed rule per scale (a scale with fewer than min_neighbours neighbours does not
+            hold); s0 = 1 when at least scales_min scales hold (tl_leafwood_seed_scales).  The vote keeps `radius`.  Without `scales`
+            nothing changes.  Recommended for leaf-on broadleaves: scales 0.1 0.3 0.4 with scales_min 2 (the grid of §26).
+
+Known limits: the seed is one scale unless `scales` is given; conifer needles along a twig are linear like the twig; a stem patch scanned from one side at long
 range may fall under min_neighbours; the features see the neighbouring trees' rows while the vote does not; the thresholds are defaults,
 not fitted to any species.
 
@@ -54,7 +60,8 @@ _HELP = dict(radius="radius of the feature and vote neighbourhoods, metres", min
              min_component="a connected component of fewer wood voxels than this is dropped",
              filter="1: the branch and wood stages read the wood rows only; 0: they read every row")
 
-__all__ = ["LEAFWOOD_DEFAULTS", "LEAFWOOD_COLUMNS", "LEAFWOOD_INT_COLUMNS", "check_params", "add_arguments", "params_of", "write_leafwood"]
+__all__ = ["LEAFWOOD_DEFAULTS", "LEAFWOOD_COLUMNS", "LEAFWOOD_INT_COLUMNS", "check_params", "add_arguments", "params_of", "write_leafwood",
+           "LEAFWOOD_SCALE_DEFAULTS", "check_scales", "scales_of"]
 
 
 def stages_of(p):
@@ -105,6 +112,50 @@ def check_params(cfg=None, **kw):
     return p
 
 
+LEAFWOOD_SCALE_DEFAULTS = dict(scales=None, scales_min=1)
+MAX_SCALES = 4                                                                                   # TL_FEAT_MAX_SCALES
+
+
+def check_scales(cfg=None, **kw):
+    """The two scale parameters of the seed as a dict of plain values: `scales` None (the one-scale seed at `radius`) or a
+    list of 1..4 finite radii > 0 in strictly ascending order, `scales_min` an integer in 1..len(scales) (1 with scales None).
+    ValueError otherwise.  Touches no GPU."""
+    s = dict(LEAFWOOD_SCALE_DEFAULTS)
+    for src in (cfg or {}), kw:
+        for k, v in src.items():
+            if k not in LEAFWOOD_SCALE_DEFAULTS:
+                raise ValueError(f"unknown leafwood scale parameter {k!r}; expected one of {tuple(LEAFWOOD_SCALE_DEFAULTS)}")
+            if v is not None:
+                s[k] = v
+    m = s["scales_min"]
+    if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, float, np.integer, np.floating)) or not np.isfinite(m) or int(m) != m:
+        raise ValueError(f"scales_min must be an integer, got {m!r}")
+    s["scales_min"] = int(m)
+    if s["scales"] is None:
+        if s["scales_min"] != 1:
+            raise ValueError(f"scales_min must be 1 without scales, got {m!r}")
+        return s
+    from .features import check_radii
+    try:
+        s["scales"] = check_radii(s["scales"])
+    except ValueError as e:
+        raise ValueError(f"scales: {e}") from None
+    if not 1 <= s["scales_min"] <= len(s["scales"]):
+        raise ValueError(f"scales_min must be in 1..{len(s['scales'])}, got {m!r}")
+    return s
+
+
+def seed_flags_scales(feats, p, scales_min):
+    """tl_leafwood_seed_scales: feats f32 [n, S, 4] on the device (FEATURES at every scale) -> u8 [n]."""
+    import torch
+    from .. import _hip
+    n, S = feats.shape[0], feats.shape[1]
+    flag = torch.empty(n, dtype=torch.uint8, device=feats.device)
+    _hip.check(_hip.lib().tl_leafwood_seed_scales(_hip.ptr(feats), n, S, _lib_params(p), int(scales_min), _hip.ptr(flag), _hip.stream()),
+               "tl_leafwood_seed_scales")
+    return flag
+
+
 def _lib_params(p):
     from .. import _hip
     return _hip.LeafwoodParams(**dict(p, filter=int(p["filter"])))
@@ -143,17 +194,20 @@ def vote_rounds(sx, skeys, ext, pieces, tree_sorted, flag, p, mark=None):
     return out
 
 
-def leafwood_stage(xyz, kept_lab, T, tree, p, mark):
+def leafwood_stage(xyz, kept_lab, T, tree, p, mark, scales=None):
     """The stage on the device, without a host synchronise apart from the lengths the sorts read back.  xyz f64 [m, 3]: the gathered rows in
     label order, kept_lab i64 [m]: their labels, tree f64 [T, 4] = px, py, z_ref, z_top per tree, p: checked parameters, mark(name): closes
     a timed stage (stages_of(p)).  Returns a dict of device tensors: wood u8 [m] (in label order), seed and voted u8 [m] (the flags behind
     rules 2 and 3), wood_points, rows, components i64 [T], top_z f64 [T] (-inf without a wood row) and err i32 [1] (or None: no rows); the
-    caller raises util.branches.branch_error() when err reads non-zero."""
+    caller raises util.branches.branch_error() when err reads non-zero.
+    scales: None (the seed at `radius`, nothing else launched) or a checked dict of check_scales with a list of radii: the features of
+    all of them from one sort at max(scales) and one tl_eigen_features_scales, the seed by tl_leafwood_seed_scales; the vote keeps
+    `radius` and its own sort at `radius` (shared when max(scales) == radius).  The stage names do not change."""
     import torch
     from .. import _hip
     from . import branches as _branches
     from .features import FEATURE_NAMES
-    from .prepare import eigen_features_sorted, feature_pieces, sorted_cells
+    from .prepare import eigen_features_scales_sorted, eigen_features_sorted, feature_pieces, sorted_cells
     lib, dev, m = _hip.lib(), xyz.device, len(xyz)
     i64, i32, u8 = (dict(dtype=t, device=dev) for t in (torch.int64, torch.int32, torch.uint8))
     out = dict(wood=torch.zeros(m, **u8), seed=torch.zeros(m, **u8), voted=torch.zeros(m, **u8), wood_points=torch.zeros(T, **i64),
@@ -163,13 +217,33 @@ def leafwood_stage(xyz, kept_lab, T, tree, p, mark):
             mark(name)
         return out
     r = p["radius"]
-    sx, skeys, perm, ext = sorted_cells(xyz, r)
-    pieces = feature_pieces(skeys)
-    mark(STAGES[0])
-    feats = eigen_features_sorted(sx, skeys, ext, pieces, r, [FEATURE_NAMES.index(k) for k in FEATURES])
-    mark(STAGES[1])
-    seed = seed_flags(feats, p)
-    mark(STAGES[2])
+    ids = [FEATURE_NAMES.index(k) for k in FEATURES]
+    if scales is None or scales["scales"] is None:
+        sx, skeys, perm, ext = sorted_cells(xyz, r)
+        pieces = feature_pieces(skeys)
+        mark(STAGES[0])
+        feats = eigen_features_sorted(sx, skeys, ext, pieces, r, ids)
+        mark(STAGES[1])
+        seed = seed_flags(feats, p)
+        mark(STAGES[2])
+    else:
+        radii = scales["scales"]
+        fx, fkeys, fperm, fext = sorted_cells(xyz, radii[-1])
+        fpieces = feature_pieces(fkeys)
+        if radii[-1] == r:                                                             # the vote's sort is the features' sort
+            sx, skeys, perm, ext, pieces = fx, fkeys, fperm, fext, fpieces
+        else:
+            sx, skeys, perm, ext = sorted_cells(xyz, r)
+            pieces = feature_pieces(skeys)
+        mark(STAGES[0])
+        feats = eigen_features_scales_sorted(fx, fkeys, fext, fpieces, radii, ids)
+        mark(STAGES[1])
+        seed = seed_flags_scales(feats, p, scales["scales_min"])
+        if fperm is not perm:                                                          # from the features' order to the vote's
+            rows = torch.empty_like(seed)
+            rows[fperm] = seed
+            seed = rows.index_select(0, perm)
+        mark(STAGES[2])
     voted = vote_rounds(sx, skeys, ext, pieces, kept_lab.index_select(0, perm).to(torch.int32), seed, p, mark)
     out["seed"][perm], out["voted"][perm] = seed, voted                                # back to label order
     flag = out["voted"]
@@ -249,6 +323,15 @@ def add_arguments(ap):
         opt = "--leafwood-" + k.replace("_", "-")
         if opt not in ap._option_string_actions:
             ap.add_argument(opt, type=int if k in _INT + ("filter",) else float, default=int(v) if k == "filter" else v, help=_HELP[k])
+    if "--leafwood-scales" not in ap._option_string_actions:
+        ap.add_argument("--leafwood-scales", type=float, nargs="+", default=None, metavar="R",
+                        help="1 to 4 ascending radii, metres: the seed rule is applied at each of them (the vote keeps --leafwood-radius)")
+        ap.add_argument("--leafwood-scales-min", type=int, default=1, metavar="K", help="a row is a seed when the rule holds at K of the scales or more")
+
+
+def scales_of(a):
+    """The two scale options of add_arguments as check_scales takes them."""
+    return dict(scales=a.leafwood_scales, scales_min=a.leafwood_scales_min)
 
 
 def params_of(a):
@@ -273,6 +356,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     try:
         cfg = check_params(params_of(a))
+        sc = check_scales(scales_of(a))
         params = _inventory.check_params(_inventory.params_of(a))
         terrain_cfg = _terrain.check_params(_terrain.params_of(a))
     except ValueError as e:
@@ -283,7 +367,8 @@ def main(argv=None):
     data = load_forest(a.forest)
     if data.shape[1] != 4:
         ap.error(f"--forest {a.forest}: expected N x 4 (x y z label), got {data.shape}")
-    inv = _inventory.cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, leafwood=True, leafwood_cfg=cfg, **params)
+    inv = _inventory.cloud_inventory(data, terrain=a.terrain, terrain_cfg=terrain_cfg if a.terrain else None, leafwood=True, leafwood_cfg=cfg,
+                                      leafwood_scales=sc["scales"], leafwood_scales_min=sc["scales_min"], **params)
     write_leafwood(a.out, inv)
     if a.csv:
         _inventory.write_inventory(a.csv, inv)

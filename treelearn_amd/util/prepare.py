@@ -143,6 +143,38 @@ def _eigen_features(points, search_radius, ids, replace_nan=True):
     return torch.where(finite, out, mean.expand_as(out)).contiguous()
 
 
+def eigen_features_scales_sorted(sx, skeys, ext, pieces, radii, ids):
+    """tl_eigen_features_scales on points sorted by cells of max(radii): f32 [n, len(radii), len(ids)] in sorted order, NaNs left in.
+    Every scale is, bit for bit, eigen_features_sorted on the same arrays at that radius."""
+    from .features import check_radii
+    radii = check_radii(radii)
+    L = _hip.lib()
+    n, S, F = len(sx), len(radii), len(ids)
+    out = torch.empty((n, S, F), dtype=torch.float32, device=sx.device)
+    cols, rad = (ctypes.c_int32 * F)(*ids), (ctypes.c_double * S)(*radii)
+    _hip.check(L.tl_eigen_features_scales(_hip.ptr(sx), _hip.ptr(skeys), n, ctypes.cast(rad, ctypes.c_void_p), S, _I64x2(ext[0], ext[1]), _hip.ptr(pieces),
+                                          len(pieces), ctypes.cast(cols, ctypes.c_void_p), F, _hip.ptr(out), _hip.stream()), "tl_eigen_features_scales")
+    return out
+
+
+def compute_features_scales(points, radii, feature_names, replace_nan=True):
+    """points [N, 3] -> float32 [N, S, F]: the features of `feature_names` (any of util.features.FEATURE_NAMES, no duplicates) at every
+    radius of `radii` (1 .. 4, strictly ascending), in input order, from one cell sort at max(radii), one work table and one launch of
+    tl_eigen_features_scales.  NaNs are replaced per (scale, column) by the mean of that column's finite values at that scale, the rule
+    of compute_features; replace_nan=False leaves them in."""
+    from .features import check_radii, feature_ids
+    ids, radii = feature_ids(feature_names), check_radii(radii)                       # ValueError before any GPU work
+    xyz = _dev_f64(points)
+    sx, skeys, perm, ext = sorted_cells(xyz, radii[-1])
+    v = eigen_features_scales_sorted(sx, skeys, ext, feature_pieces(skeys), radii, ids)
+    out = torch.empty_like(v); out[perm] = v
+    if not replace_nan:
+        return out
+    finite = ~torch.isnan(out)
+    mean = (torch.where(finite, out.double(), torch.zeros((), dtype=torch.float64, device=out.device)).sum(0) / finite.sum(0).double()).float()
+    return torch.where(finite, out, mean.expand_as(out)).contiguous()
+
+
 def propagate_to_original(preds_voxelized, trace):
     """Every original point takes the prediction of its voxel (util/pipeline.py:441-452 without the hash dictionary)."""
     p = preds_voxelized if torch.is_tensor(preds_voxelized) else torch.from_numpy(np.asarray(preds_voxelized))

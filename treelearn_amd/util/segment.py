@@ -160,7 +160,7 @@ def segment_from_pointwise(coords, offset_predictions, instance_preds, shape_cfg
 def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=None, return_type="original", logger=None,
                    return_pointwise=False, inventory=False, inventory_cfg=None, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None,
                    crown=False, crown_cfg=None, canopy=False, canopy_cfg=None, branches=False, branch_cfg=None, wood=False,
-                   wood_cfg=None, leafwood=False, leafwood_cfg=None):
+                   wood_cfg=None, leafwood=False, leafwood_cfg=None, leafwood_scales=None, leafwood_scales_min=None):
     """points: N x 3 or N x 4 (x y z [label]) f64, host or device.  Returns numpy arrays: coords (f64, input frame), labels (i64),
     categories (per tree 1..T, index into CATEGORIES), and with return_pointwise the arrays of pipeline.py:100-111 (ensembled rows).
     inventory=True adds result["inventory"]: util.inventory.tree_inventory of the returned coords / labels, computed on the device in
@@ -180,7 +180,8 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
     wood=True implies branches=True and adds util.wood's columns and result["inventory"]["cylinders"] (the fitted circle, radius and
     frustum of every skeleton node); wood_cfg holds any of util.wood's parameters.
     leafwood=True implies inventory=True and adds util.leafwood's columns and result["inventory"]["leafwood"] (wood u8 [N], the wood flag
-    of every row, row-aligned with coords, and the parameters); leafwood_cfg holds any of util.leafwood's parameters."""
+    of every row, row-aligned with coords, and the parameters); leafwood_cfg holds any of util.leafwood's parameters, leafwood_scales and
+    leafwood_scales_min the scales of its seed."""
     extra = {}
     if branches or wood:
         from .branches import check_params as check_branches
@@ -190,8 +191,9 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
         from .wood import check_params as check_wood
         extra.update(wood=True, wood_cfg=check_wood(wood_cfg))                        # before any GPU work
     if leafwood:
-        from .leafwood import check_params as check_leafwood
-        extra.update(leafwood=True, leafwood_cfg=check_leafwood(leafwood_cfg))        # before any GPU work
+        from .leafwood import check_params as check_leafwood, check_scales
+        check_scales(scales=leafwood_scales, scales_min=leafwood_scales_min)          # before any GPU work
+        extra.update(leafwood=True, leafwood_cfg=check_leafwood(leafwood_cfg), leafwood_scales=leafwood_scales, leafwood_scales_min=leafwood_scales_min)
         inventory = True
     if canopy:
         from .canopy import canopy_model, check_params as check_canopy, stand_summary
@@ -492,6 +494,7 @@ def parse_args(argv=None):
         _branches.check_params(_branches.params_of(a))
         _wood.check_params(_wood.params_of(a))
         _leafwood.check_params(_leafwood.params_of(a))
+        _leafwood.check_scales(_leafwood.scales_of(a))
     except ValueError as e:
         ap.error(str(e))
     check_formats(a.formats)
@@ -542,7 +545,8 @@ def main(argv=None):
                              canopy=a.canopy, canopy_cfg=_canopy.params_of(a) if a.canopy else None,
                              branches=a.branches or a.wood, branch_cfg=_branches.params_of(a) if a.branches or a.wood else None,
                              wood=a.wood, wood_cfg=_wood.params_of(a) if a.wood else None,
-                             leafwood=a.leafwood, leafwood_cfg=_leafwood.params_of(a) if a.leafwood else None)
+                             leafwood=a.leafwood, leafwood_cfg=_leafwood.params_of(a) if a.leafwood else None,
+                             leafwood_scales=a.leafwood_scales, leafwood_scales_min=a.leafwood_scales_min)
     plot_name = os.path.splitext(os.path.basename(a.forest))[0]
     save_results(res, a.out, plot_name, a.formats, save_treewise=not a.no_treewise, save_pointwise=a.save_pointwise)
     cats = np.bincount(res["categories"], minlength=3)
