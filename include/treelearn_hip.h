@@ -979,6 +979,46 @@ int tl_grid_metrics(const double* sorted_h, int64_t n, const int64_t* start, int
                     int n_percentiles, double layer, int L, double* metrics, int32_t* counts, int32_t* layers, int32_t* n_clipped,
                     tl_stream_t stream);
 
+/* ------------------------------------------------------------------ pictures of clouds and rasters (csrc/tl_render.hip)
+ * Orthographic point splats with a depth test, rasters as depth-keyed pixels, and a shading pass.  The semantics are the project's own
+ * (restated in numpy float64 in tests/render_restatement.py); all arithmetic is f64 in plain operators, no fma contraction, no
+ * transcendental function; the only atomics are integer maxima, so every output has the same bits for any row order.
+ * The canvas is keys u64[height, width], width and height in 1 .. 16384, image row 0 at the top; key 0 is an empty pixel.  A key is
+ * image << 32 | rgb: rgb = r << 16 | g << 8 | b, image = the order-preserving u32 image of a float32 depth (bits ^ 0xFFFFFFFF when the
+ * sign bit is set, else bits | 0x80000000; no finite or infinite depth maps to 0).  A larger depth is nearer the viewer and wins; equal
+ * depths are settled by the larger rgb.
+ * tl_splat: pts f32 or f64 by dtype_f64, row stride ld >= 3 elements, n rows, widened exactly.  views f64[n_views, 18] (device): u[3]
+ *   screen right, v[3] screen up, w[3] towards the viewer, c[3] the centre, s pixels per metre, x0, y0, vw, vh the viewport on the
+ *   canvas (integers held in f64, inside the canvas: the caller checks that), one reserved 0.  vid i32[n] or null (every row in view 0):
+ *   a negative vid skips the row, a vid >= n_views skips it and sets flags[0].  q = p - c; a = (u0 * qx + u1 * qy) + u2 * qz, b and d
+ *   likewise with v and w; px = floor(a * s + (x0 + vw / 2)), py = floor((y0 + vh / 2) - b * s); depth = float32(d + 0.0), round to
+ *   nearest even.  A row with a coordinate that is not finite, or a depth that is not finite as float32, is skipped and sets flags[0].
+ *   The footprint of `size` = k in 1 .. 9 is px - (k - 1) / 2 .. px + k / 2 and the same in y (integer divisions); each of its pixels
+ *   inside the row's viewport (and the canvas) takes atomicMax(keys, key).  keys is NOT cleared: layers accumulate, the caller clears
+ *   once.  flags i32[4] (device): flags[0] is set to 1 as said and otherwise left as it is; flags[1 .. 3] are reserved.
+ *   The colour by mode: 0 the argument rgb; 1 attr = labels i64[n] through lut u32[n_lut], n_lut >= 3: label < 0 -> lut[0], 0 -> lut[1],
+ *   else lut[2 + (label - 1) mod (n_lut - 2)]; 2 attr = values f32 or f64 by attr_f64 through lut u32[256] with lo < hi, both finite:
+ *   a NaN value -> nan_rgb, else lut[floor((v - lo) / (hi - lo) * 255 + 0.5) clamped to 0 .. 255]; 3 attr = rgb u8[n, 3].  Only the low
+ *   24 bits of a lut entry are used.  A row whose whole footprint is outside its viewport does not read its attribute.
+ * tl_raster_keys: grid f64[ny, nx] with grid row 0 the lowest y, an integer zoom >= 1, placed at pixel (x0, y0); the block of ny * zoom
+ *   x nx * zoom pixels must lie inside the canvas.  Pixel (py, px) of the block reads cell (ny - 1 - py / zoom, px / zoom): NaN -> key 0,
+ *   else the image of float32(value + 0.0) << 32 | the mode-2 colour.  Plain stores: the block is overwritten.
+ * tl_render_shade: out u8[height, width, 3]; depth f32[height, width] or null.  A pixel with key 0 gets `background` (depth NaN).  Any
+ *   other: d_c = its decoded depth as f64; the neighbours at (dy, dx) in {-radius, 0, radius}^2 without the centre, in row-major order,
+ *   contribute d_n - d_c where that is > 0, and 0 where it is not or the neighbour is outside the image or empty; o = their sum in that
+ *   order / 8.0; shade = 1.0 / (1.0 + strength * o); a channel is floor(ch * shade + 0.5) (clamped to 0 .. 255, NaN -> 0).
+ * A null or misaligned pointer, width or height outside 1 .. 16384, n < 0, ld < 3, n_views outside 1 .. 2^20, mode outside 0 .. 3, size
+ * outside 1 .. 9, an rgb beyond 24 bits, n_lut < 3 (mode 1) or != 256 (mode 2), lo >= hi or not finite, a missing attr or lut for the
+ * mode, zoom < 1, a raster block outside the canvas, radius outside 1 .. 16, a strength below 0 or not finite, out or depth aliasing
+ * keys: TL_ERR_ARG, nothing launched.  Then n = 0 or an empty grid: TL_OK without a kernel launch. */
+int tl_splat(const void* pts, int dtype_f64, int64_t ld, int64_t n, const int32_t* vid, const double* views, int n_views, int mode, uint32_t rgb,
+             const void* attr, int attr_f64, const uint32_t* lut, int n_lut, double lo, double hi, uint32_t nan_rgb, int size, uint64_t* keys,
+             int width, int height, int32_t* flags, tl_stream_t stream);
+int tl_raster_keys(const double* grid, int nx, int ny, int zoom, int x0, int y0, const uint32_t* lut, double lo, double hi, uint64_t* keys,
+                   int width, int height, tl_stream_t stream);
+int tl_render_shade(const uint64_t* keys, int width, int height, int radius, double strength, uint32_t background, uint8_t* out, float* depth,
+                    tl_stream_t stream);
+
 /* ------------------------------------------------------------------ LAS point records (csrc/tl_las.hip)
  * The record passes of the LAS reader and writer (treelearn_amd/util/las.py parses and writes the headers on the host).  The layout is
  * the ASPRS one and the rules are restated in numpy in tests/las_restatement.py; all arithmetic is f64 in plain operators, no fma

@@ -160,7 +160,8 @@ def segment_from_pointwise(coords, offset_predictions, instance_preds, shape_cfg
 def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=None, return_type="original", logger=None,
                    return_pointwise=False, inventory=False, inventory_cfg=None, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None,
                    crown=False, crown_cfg=None, canopy=False, canopy_cfg=None, branches=False, branch_cfg=None, wood=False,
-                   wood_cfg=None, leafwood=False, leafwood_cfg=None, leafwood_scales=None, leafwood_scales_min=None):
+                   wood_cfg=None, leafwood=False, leafwood_cfg=None, leafwood_scales=None, leafwood_scales_min=None, preview=False,
+                   preview_cfg=None):
     """points: N x 3 or N x 4 (x y z [label]) f64, host or device.  Returns numpy arrays: coords (f64, input frame), labels (i64),
     categories (per tree 1..T, index into CATEGORIES), and with return_pointwise the arrays of pipeline.py:100-111 (ensembled rows).
     inventory=True adds result["inventory"]: util.inventory.tree_inventory of the returned coords / labels, computed on the device in
@@ -181,8 +182,13 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
     frustum of every skeleton node); wood_cfg holds any of util.wood's parameters.
     leafwood=True implies inventory=True and adds util.leafwood's columns and result["inventory"]["leafwood"] (wood u8 [N], the wood flag
     of every row, row-aligned with coords, and the parameters); leafwood_cfg holds any of util.leafwood's parameters, leafwood_scales and
-    leafwood_scales_min the scales of its seed."""
+    leafwood_scales_min the scales of its seed.
+    preview=True adds result["preview"]: util.render.render_forest's pictures (name -> u8 [H, W, 3]) of the returned cloud and of
+    whatever else was computed, rendered from the arrays still on the device; preview_cfg holds any of util.render's parameters."""
     extra = {}
+    if preview:
+        from .render import check_params as check_preview, render_forest
+        preview_cfg = check_preview(preview_cfg)                                      # before any GPU work
     if branches or wood:
         from .branches import check_params as check_branches
         extra = dict(branches=True, branch_cfg=check_branches(branch_cfg))            # before any GPU work
@@ -272,6 +278,12 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
         _log(logger, "computing the canopy height model")
         result["canopy"] = canopy_model(r["coords"], labels=r["labels"], height_above_ground=hag, offset=mean, **canopy_cfg).to_host()
         result["stand"] = stand_summary(result["canopy"], result.get("inventory"))
+    if preview:
+        _log(logger, "rendering the previews")
+        shown = dict(result, coords=r["coords"], labels=r["labels"])
+        if terrain:
+            shown["height_above_ground"] = hag
+        result["preview"] = {k: host(v) for k, v in render_forest(shown, **preview_cfg).items()}
     if return_pointwise:
         pw = dict(coords=coords, offset_predictions=off, offset_labels=offl, semantic_prediction_logits=sem, semantic_labels=seml,
                   instance_labels=instl, backbone_feats=bb, input_feats=infeat, instance_preds=inst, instance_preds_after_initial_clustering=initial)
@@ -334,7 +346,8 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
     the inventory holds stem profiles; crown_profiles.npz (util.crown.write_crown_profiles) when it holds crown profiles; skeletons.npz
     (util.branches.write_skeletons) when it holds "skeleton"; cylinders.npz (util.wood.write_cylinders) when it holds "cylinders"; leafwood.npy
     (util.leafwood.write_leafwood) when it holds "leafwood"; canopy.npz and stand.json
-    (util.canopy.write_canopy, write_stand) when the result holds a canopy."""
+    (util.canopy.write_canopy, write_stand) when the result holds a canopy; preview/<name>.png (util.render.write_png) when it holds
+    previews."""
     save_formats = list(save_formats)
     check_formats(save_formats)
     coords, labels = np.asarray(result["coords"], np.float64), np.asarray(result["labels"], np.int64)
@@ -403,6 +416,9 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
         os.makedirs(out_dir, exist_ok=True)
         write_canopy(os.path.join(out_dir, "canopy.npz"), result["canopy"])
         write_stand(os.path.join(out_dir, "stand.json"), result["stand"])
+    if "preview" in result:
+        from .render import write_previews
+        write_previews(os.path.join(out_dir, "preview"), result["preview"])
     if save_pointwise and "pointwise" in result:
         pw = result["pointwise"]
         pdir = os.path.join(out_dir, "pointwise_results")
@@ -484,6 +500,9 @@ def parse_args(argv=None):
     ap.add_argument("--canopy", action="store_true", help="write canopy.npz (canopy height model, tree tops, grid metrics) and stand.json (implies --terrain)")
     from . import canopy as _canopy
     _canopy.add_arguments(ap)
+    ap.add_argument("--preview", action="store_true", help="write preview/<name>.png: the segmented cloud from the top and the south, heights, the contact sheet of the trees, and the DTM, CHM and wood flags where they are computed")
+    from . import render as _render
+    _render.add_arguments(ap, "preview-")
     a = ap.parse_args(argv)
     try:
         check_params(params_of(a))
@@ -495,6 +514,7 @@ def parse_args(argv=None):
         _wood.check_params(_wood.params_of(a))
         _leafwood.check_params(_leafwood.params_of(a))
         _leafwood.check_scales(_leafwood.scales_of(a))
+        _render.check_params(_render.params_of(a, "preview-"))
     except ValueError as e:
         ap.error(str(e))
     check_formats(a.formats)
@@ -535,7 +555,7 @@ def main(argv=None):
                     tau_vert=a.tau_vert, tau_off=a.tau_off)
     shape = dict(SHAPE_CFG, alpha=a.alpha, buffer_size_to_determine_edge_trees=a.edge_buffer, outer_remove=a.outer_remove)
     with torch.no_grad():
-        from . import branches as _branches, canopy as _canopy, crown as _crown, leafwood as _leafwood, stem as _stem, terrain as _terrain, wood as _wood
+        from . import branches as _branches, canopy as _canopy, crown as _crown, leafwood as _leafwood, render as _render, stem as _stem, terrain as _terrain, wood as _wood
         from .inventory import params_of
         res = segment_forest(points, model, sample, grouping, shape, a.return_type, logger, return_pointwise=a.save_pointwise,
                              inventory=a.inventory, inventory_cfg=params_of(a) if a.inventory or a.stem or a.crown or a.branches or a.wood or a.leafwood else None,
@@ -546,7 +566,8 @@ def main(argv=None):
                              branches=a.branches or a.wood, branch_cfg=_branches.params_of(a) if a.branches or a.wood else None,
                              wood=a.wood, wood_cfg=_wood.params_of(a) if a.wood else None,
                              leafwood=a.leafwood, leafwood_cfg=_leafwood.params_of(a) if a.leafwood else None,
-                             leafwood_scales=a.leafwood_scales, leafwood_scales_min=a.leafwood_scales_min)
+                             leafwood_scales=a.leafwood_scales, leafwood_scales_min=a.leafwood_scales_min,
+                             preview=a.preview, preview_cfg=_render.params_of(a, "preview-") if a.preview else None)
     plot_name = os.path.splitext(os.path.basename(a.forest))[0]
     save_results(res, a.out, plot_name, a.formats, save_treewise=not a.no_treewise, save_pointwise=a.save_pointwise)
     cats = np.bincount(res["categories"], minlength=3)
