@@ -979,6 +979,37 @@ int tl_grid_metrics(const double* sorted_h, int64_t n, const int64_t* start, int
                     int n_percentiles, double layer, int L, double* metrics, int32_t* counts, int32_t* layers, int32_t* n_clipped,
                     tl_stream_t stream);
 
+/* ------------------------------------------------------------------ light under the canopy (csrc/tl_light.hip)
+ * A bit grid of the occupied voxels of a cloud and a ray march through it: per origin and zenith ring, how the rays of a direction table
+ * end.  The semantics are the project's own (restated in numpy float64 in tests/light_restatement.py); all arithmetic is f64 in plain
+ * operators, no fma contraction; the only atomics are integer ones, so every output has the same bits for any row order.
+ * The grid follows the terrain's rule in three axes: a row's voxel is (floor(x / voxel) - ix0, floor(y / voxel) - iy0, floor(z / voxel) -
+ * iz0); nx, ny, nz <= 8192 and nx * ny * nz <= 2^31 without an owner grid, <= 2^28 with one.  occ u32[nz, ny, ceil(nx / 32)]: bit ix % 32
+ * of word ix / 32 of row (iz, iy).  owner i32[nz, ny, nx].
+ * tl_light_voxels: pts f32 or f64 by dtype_f64, row stride ld >= 3 elements, n rows, widened exactly.  occ (overwritten) gets the bit of
+ *   every row's voxel.  labels i64[n] and owner go together, both given or both null: owner (overwritten) = the largest label >= 0 among
+ *   the voxel's rows, -1 for a voxel without one.  *err (device, overwritten) = 1 when a coordinate is not finite, a row lies outside the
+ *   grid or a label is outside the i32 range (the row is skipped and the caller raises), else 0.
+ * tl_light_march: origins f64[n_origins, 3], skip i32[n_origins] or null (-1 for all), dirs f64[n_dirs, 3] (the host checks that they are
+ *   finite and of unit length), ring i32[n_dirs] in 0 .. n_rings - 1 (a ray whose ring is outside that range is counted nowhere).  For
+ *   origin o and direction d: i_a = floor(o_a / voxel) - i0_a per axis; an origin outside the grid (a NaN included) gets status 1 and no
+ *   counts, any other status 0.  s_a = the sign of d_a; t_a = ((i0_a + i_a + (s_a > 0 ? 1 : 0)) * voxel - o_a) / d_a for s_a != 0, +inf
+ *   for s_a = 0, always from the integer index.  Repeat: take the axis of the smallest t (ties to x, then y, then z), t_enter = t_a; if
+ *   t_enter > max_range exit with code 2; i_a += s_a; if the index left the grid exit with code 1 through the top (a = z, s > 0) and 3
+ *   through a side or the bottom; recompute t_a from the new index; the voxel entered is a hit when its bit is set and (skip < 0 or there
+ *   is no owner grid or owner != skip); at min_hits hits exit with code 0 and first = t_enter.  The origin's own voxel is never tested.
+ *   counts i32[n_origins, n_rings, 4] (overwritten): the rays of the origin and ring per exit code.  status i32[n_origins].  code
+ *   u8[n_origins, n_dirs] or null (255 for an origin outside the grid); first f64[n_origins, n_dirs] or null (NaN unless the code is 0).
+ *   One wave serves 64 consecutive directions of one origin; a lane's walk is bounded by nx + ny + nz steps.
+ * A null or misaligned pointer, a negative size, ld < 3, a voxel that is not positive and finite, a grid beyond the limits, rows or
+ * origins with an empty grid, n_rings outside 1 .. 65536, min_hits < 1, a max_range that is not positive and finite: TL_ERR_ARG, nothing
+ * touched.  Then n = 0 or n_origins = 0: TL_OK without a kernel launch; tl_light_voxels still clears occ, owner and *err. */
+int tl_light_voxels(const void* pts, int dtype_f64, int64_t ld, int64_t n, const int64_t* labels, double voxel, int64_t ix0, int64_t iy0,
+                    int64_t iz0, int nx, int ny, int nz, uint32_t* occ, int32_t* owner, int32_t* err, tl_stream_t stream);
+int tl_light_march(const double* origins, const int32_t* skip, int64_t n_origins, const double* dirs, const int32_t* ring, int64_t n_dirs,
+                   int n_rings, const uint32_t* occ, const int32_t* owner, double voxel, int64_t ix0, int64_t iy0, int64_t iz0, int nx, int ny,
+                   int nz, double max_range, int min_hits, int32_t* counts, int32_t* status, uint8_t* code, double* first, tl_stream_t stream);
+
 /* ------------------------------------------------------------------ pictures of clouds and rasters (csrc/tl_render.hip)
  * Orthographic point splats with a depth test, rasters as depth-keyed pixels, and a shading pass.  The semantics are the project's own
  * (restated in numpy float64 in tests/render_restatement.py); all arithmetic is f64 in plain operators, no fma contraction, no

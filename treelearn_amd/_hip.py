@@ -231,6 +231,9 @@ PROTOTYPES = {
     "tl_chm_tops": (_i32, [_vp, _i32, _i32, _i32, _c.c_double, _vp, _vp]),
     "tl_canopy_keys": (_i32, [_vp, _i32, _i64, _i64, _vp, _c.c_double, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "tl_grid_metrics": (_i32, [_vp, _i64, _vp, _i64, _c.c_double, _c.POINTER(_c.c_double), _i32, _c.c_double, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "tl_light_voxels": (_i32, [_vp, _i32, _i64, _i64, _vp, _c.c_double, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "tl_light_march": (_i32, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _c.c_double, _i64, _i64, _i64, _i32, _i32, _i32, _c.c_double, _i32,
+                              _vp, _vp, _vp, _vp, _vp]),
     "tl_splat": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _i32, _i32, _c.c_uint32, _vp, _i32, _vp, _i32, _c.c_double, _c.c_double, _c.c_uint32, _i32,
                         _vp, _i32, _i32, _vp, _vp]),
     "tl_raster_keys": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _c.c_double, _c.c_double, _vp, _i32, _i32, _vp]),

@@ -119,7 +119,7 @@ def _device_inputs(coords, labels):
 def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh_max_radius=1.0, dbh_min_points=8, crown_cell=0.25,
                    offset=None, stages=None, terrain=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None, branches=False,
                    branch_cfg=None, wood=False, wood_cfg=None, leafwood=False, leafwood_cfg=None, leafwood_scales=None,
-                   leafwood_scales_min=None):
+                   leafwood_scales_min=None, light=False, light_cfg=None):
     """coords [N, 3] float32 or float64 (a row stride of 3 or 4 elements is read in place), labels [N] integers; numpy arrays or tensors,
     on the host or the device.  Returns a dict of numpy arrays of length T = max(label), keyed by COLUMNS (tree_id = 1..T).
     `offset` (3 values) is added to x, y, z, z_low, z_top, dbh_x, dbh_y at the end -- the un-centring of segment_forest.
@@ -138,7 +138,12 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
     every input row, 0 for a label < 1) and the parameters; leafwood_cfg holds any of util.leafwood's parameters; leafwood_scales (1 to 4
     ascending radii) and leafwood_scales_min make the seed a count over scales (util.leafwood.check_scales) and are recorded
     in that dict.  With its `filter`
-    (the default) the branch and wood stages read the wood rows only."""
+    (the default) the branch and wood stages read the wood rows only.
+    `light`: True adds util.light's LIGHT_COLUMNS after every other column: how much sky the top of the tree sees past its neighbours
+    (DESIGN §28); light_cfg holds any of util.light's parameters."""
+    if light:
+        from . import light as _light
+        light_cfg = _light.check_params(light_cfg)                                    # before any GPU work
     if leafwood:
         from . import leafwood as _leafwood
         leafwood_cfg = _leafwood.check_params(leafwood_cfg)                           # before any GPU work
@@ -237,6 +242,8 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
         branch_dev = _branches.branch_stage(wood_xyz, wood_lab, T, tree, branch_cfg, mark)
     if wood:
         wood_dev = _wood.wood_stage(wood_xyz, branch_dev, T, wood_cfg, mark)
+    if light:
+        light_out = _light.light_stage(c, lab, T, light_cfg, mark)
 
     table_h, counts_h, cells_h = table.cpu().numpy(), counts.cpu().numpy(), cells.cpu().numpy()
     if terrain is not None:
@@ -298,26 +305,31 @@ def tree_inventory(coords, labels, *, slice_height=1.3, slice_thickness=0.2, dbh
         out.update(_wood.to_columns(dict(out["skeleton"], xyz=branch_h["xyz"]), wood_h, branch_zref, wood_cfg, branch_cfg, off))
         mark("wood radii")
         stem_keys = stem_keys + _wood.WOOD_COLUMNS + ("cylinders",)
+    light_keys = ()
+    if light:
+        out.update(light_out)
+        light_keys = _light.LIGHT_COLUMNS
     if terrain is None:
-        return {k: out[k] for k in COLUMNS + stem_keys}
+        return {k: out[k] for k in COLUMNS + stem_keys + light_keys}
     out.update({k: np.ascontiguousarray(gtable_h[:, j]) for j, k in enumerate(_GROUND_TABLE)})
     out["dbh_ag_n"] = gcount_h
     if off is not None:
         for k, a in _GROUND_SHIFTED:
             out[k] = out[k] + off[a]
-    return {k: out[k] for k in COLUMNS + GROUND_COLUMNS + stem_keys}
+    return {k: out[k] for k in COLUMNS + GROUND_COLUMNS + stem_keys + light_keys}
 
 
 def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None, crown=False, crown_cfg=None, branches=False,
                     branch_cfg=None, wood=False, wood_cfg=None, leafwood=False, leafwood_cfg=None, leafwood_scales=None,
-                    leafwood_scales_min=None, **params):
+                    leafwood_scales_min=None, light=False, light_cfg=None, **params):
     """The inventory of an N x 4 cloud (x y z label), as the command line computes it: the coordinates are centred on their float64 mean
     on the device, as segment_forest centres its input, and the mean is handed back as `offset`.  terrain=True builds the terrain of
     the label-0 rows in the same frame (util.terrain.terrain_model, parameters in terrain_cfg) and adds the GROUND_COLUMNS; stem=True
     adds util.stem's STEM_COLUMNS and "stem_profile" (parameters in stem_cfg); crown=True adds util.crown's CROWN_COLUMNS and
     "crown_profile" (parameters in crown_cfg); branches=True adds util.branches' BRANCH_COLUMNS and "skeleton" (parameters in branch_cfg);
     wood=True implies branches=True and adds util.wood's WOOD_COLUMNS and "cylinders" (parameters in wood_cfg); leafwood=True adds
-    util.leafwood's LEAFWOOD_COLUMNS and "leafwood" (parameters in leafwood_cfg)."""
+    util.leafwood's LEAFWOOD_COLUMNS and "leafwood" (parameters in leafwood_cfg); light=True adds util.light's LIGHT_COLUMNS last
+    (parameters in light_cfg)."""
     import torch
     pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points))
     if pts.ndim != 2 or pts.shape[1] != 4:
@@ -343,6 +355,9 @@ def cloud_inventory(points, terrain=False, terrain_cfg=None, stem=False, stem_cf
         from .leafwood import check_params as check_leafwood, check_scales
         extra.update(leafwood=True, leafwood_cfg=check_leafwood(leafwood_cfg), leafwood_scales=leafwood_scales, leafwood_scales_min=leafwood_scales_min)
         check_scales(scales=leafwood_scales, scales_min=leafwood_scales_min)
+    if light:
+        from .light import check_params as check_light
+        extra.update(light=True, light_cfg=check_light(light_cfg))
     if not torch.cuda.is_available():
         raise RuntimeError("treelearn_amd.util.inventory runs on the GPU (tl_tree_inventory); there is no CPU fallback")
     pts = pts.to("cuda")
@@ -362,18 +377,20 @@ def write_inventory(path, inv, categories=None):
     after them when the inventory was taken with a terrain, then util.stem's STEM_COLUMNS when it was taken with stem=True, then
     util.crown's CROWN_COLUMNS when it was taken with crown=True, then util.branches' BRANCH_COLUMNS when it was taken with branches=True,
     then util.wood's WOOD_COLUMNS when it was taken with wood=True; util.leafwood's LEAFWOOD_COLUMNS stand between the crown and the
-    branch group when it was taken with leafwood=True (each group only when the dict holds all of it)."""
+    branch group when it was taken with leafwood=True; util.light's LIGHT_COLUMNS come last when it was taken with light=True (each group
+    only when the dict holds all of it)."""
     from .branches import BRANCH_COLUMNS, BRANCH_INT_COLUMNS
     from .crown import CROWN_COLUMNS, CROWN_INT_COLUMNS
     from .leafwood import LEAFWOOD_COLUMNS, LEAFWOOD_INT_COLUMNS
+    from .light import LIGHT_COLUMNS, LIGHT_INT_COLUMNS
     from .stem import STEM_COLUMNS
     from .wood import WOOD_COLUMNS, WOOD_INT_COLUMNS
     T = len(inv["tree_id"])
     columns = COLUMNS + (GROUND_COLUMNS if all(k in inv for k in GROUND_COLUMNS) else ()) + (STEM_COLUMNS if all(k in inv for k in STEM_COLUMNS) else ()) + \
         (CROWN_COLUMNS if all(k in inv for k in CROWN_COLUMNS) else ()) + (LEAFWOOD_COLUMNS if all(k in inv for k in LEAFWOOD_COLUMNS) else ()) + \
         (BRANCH_COLUMNS if all(k in inv for k in BRANCH_COLUMNS) else ()) + \
-        (WOOD_COLUMNS if all(k in inv for k in WOOD_COLUMNS) else ())
-    ints = INT_COLUMNS + ("dbh_ag_n", "stem_slices") + CROWN_INT_COLUMNS + LEAFWOOD_INT_COLUMNS + BRANCH_INT_COLUMNS + WOOD_INT_COLUMNS
+        (WOOD_COLUMNS if all(k in inv for k in WOOD_COLUMNS) else ()) + (LIGHT_COLUMNS if all(k in inv for k in LIGHT_COLUMNS) else ())
+    ints = INT_COLUMNS + ("dbh_ag_n", "stem_slices") + CROWN_INT_COLUMNS + LEAFWOOD_INT_COLUMNS + BRANCH_INT_COLUMNS + WOOD_INT_COLUMNS + LIGHT_INT_COLUMNS
     names = None
     if categories is not None:
         from .segment import CATEGORIES
@@ -427,9 +444,13 @@ def main(argv=None):
     ap.add_argument("--leafwood", action="store_true", help="add the leafwood columns: wood and leaf rows, wood components, wood share, highest wood; --branches and --wood then read the wood rows only")
     from . import leafwood as _leafwood
     _leafwood.add_arguments(ap)
+    ap.add_argument("--light", action="store_true", help="add the light columns: how much sky the top of every tree sees past its neighbours")
+    from . import light as _light
+    _light.add_arguments(ap)
     a = ap.parse_args(argv)
     try:
         params = check_params(params_of(a))
+        light_cfg = _light.check_params(_light.params_of(a))
         leafwood_cfg = _leafwood.check_params(_leafwood.params_of(a))
         lw_scales = _leafwood.check_scales(_leafwood.scales_of(a))
         terrain_cfg = _terrain.check_params(_terrain.params_of(a))
@@ -449,7 +470,8 @@ def main(argv=None):
                           crown=a.crown, crown_cfg=crown_cfg if a.crown else None, branches=a.branches or a.wood,
                           branch_cfg=branch_cfg if a.branches or a.wood else None, wood=a.wood, wood_cfg=wood_cfg if a.wood else None,
                           leafwood=a.leafwood, leafwood_cfg=leafwood_cfg if a.leafwood else None,
-                          leafwood_scales=lw_scales["scales"], leafwood_scales_min=lw_scales["scales_min"], **params)
+                          leafwood_scales=lw_scales["scales"], leafwood_scales_min=lw_scales["scales_min"], light=a.light,
+                          light_cfg=light_cfg if a.light else None, **params)
     write_inventory(a.out, inv)
     ok = int(np.isfinite(inv["dbh"]).sum())
     print(f"{a.forest}: {len(data)} points, {len(inv['tree_id'])} trees, {ok} with a DBH -> {a.out}")

@@ -538,8 +538,9 @@ def _raster_picture(grid, ramp_name, size, radius, strength, background, tops=No
 def render_forest(result, **cfg):
     """The pictures of a segment_forest result (arrays on the host or the device): top_labels, south_labels, top_height (by height above
     ground when the result holds one); dtm and chm when it holds a terrain and a canopy, zoomed to about the size of the cloud views, the
-    tree tops on the chm as 5-pixel white marks; leafwood when the inventory holds the flags; trees, the contact sheet.  cfg: the
-    parameters of check_params (views is not used: the views are fixed).  Returns a dict name -> u8 [H, W, 3] on the device."""
+    tree tops on the chm as 5-pixel white marks; light, the openness raster, when it holds a light model; leafwood when the inventory
+    holds the flags; trees, the contact sheet.  cfg: the parameters of check_params (views is not used: the views are fixed).  Returns a
+    dict name -> u8 [H, W, 3] on the device."""
     p = check_params(cfg)
     c, lab = _cloud(result["coords"], result["labels"])
     kw = dict(size=p["size"], splat=p["splat"], radius=p["radius"], strength=p["strength"], background=p["background"])
@@ -554,6 +555,8 @@ def render_forest(result, **cfg):
     if result.get("canopy") is not None:
         can = result["canopy"]
         out["chm"] = _raster_picture(can["chm"], "height", tops=(can["tops_i"], can["tops_j"]), **relief)
+    if result.get("light") is not None:
+        out["light"] = _raster_picture(result["light"]["openness"], "height", **relief)
     wood = (result.get("inventory") or {}).get("leafwood")
     if wood is not None:
         out["leafwood"] = render_cloud(c, views=("south",), color="wood", wood=wood["wood"], **kw)["south"]

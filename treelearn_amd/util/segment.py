@@ -161,7 +161,7 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
                    return_pointwise=False, inventory=False, inventory_cfg=None, terrain=False, terrain_cfg=None, stem=False, stem_cfg=None,
                    crown=False, crown_cfg=None, canopy=False, canopy_cfg=None, branches=False, branch_cfg=None, wood=False,
                    wood_cfg=None, leafwood=False, leafwood_cfg=None, leafwood_scales=None, leafwood_scales_min=None, preview=False,
-                   preview_cfg=None):
+                   preview_cfg=None, light=False, light_cfg=None):
     """points: N x 3 or N x 4 (x y z [label]) f64, host or device.  Returns numpy arrays: coords (f64, input frame), labels (i64),
     categories (per tree 1..T, index into CATEGORIES), and with return_pointwise the arrays of pipeline.py:100-111 (ensembled rows).
     inventory=True adds result["inventory"]: util.inventory.tree_inventory of the returned coords / labels, computed on the device in
@@ -184,7 +184,11 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
     of every row, row-aligned with coords, and the parameters); leafwood_cfg holds any of util.leafwood's parameters, leafwood_scales and
     leafwood_scales_min the scales of its seed.
     preview=True adds result["preview"]: util.render.render_forest's pictures (name -> u8 [H, W, 3]) of the returned cloud and of
-    whatever else was computed, rendered from the arrays still on the device; preview_cfg holds any of util.render's parameters."""
+    whatever else was computed, rendered from the arrays still on the device; preview_cfg holds any of util.render's parameters.
+    light=True implies terrain=True and adds result["light"] (util.light: the voxel grid and the sensor-grid rasters of openness,
+    effective LAI and gap fractions of the returned cloud; the un-centred Light.to_host()) and, with an inventory, util.light's
+    LIGHT_COLUMNS after every other column; light_cfg holds any of util.light's parameters.  With preview=True there is one more
+    picture, `light`: the openness raster."""
     extra = {}
     if preview:
         from .render import check_params as check_preview, render_forest
@@ -201,6 +205,10 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
         check_scales(scales=leafwood_scales, scales_min=leafwood_scales_min)          # before any GPU work
         extra.update(leafwood=True, leafwood_cfg=check_leafwood(leafwood_cfg), leafwood_scales=leafwood_scales, leafwood_scales_min=leafwood_scales_min)
         inventory = True
+    if light:
+        from .light import check_params as check_light, light_model
+        light_cfg = check_light(light_cfg)                                            # before any GPU work
+        terrain = True
     if canopy:
         from .canopy import canopy_model, check_params as check_canopy, stand_summary
         canopy_cfg = check_canopy(canopy_cfg)                                         # before any GPU work
@@ -278,6 +286,12 @@ def segment_forest(points, model, sample_cfg=None, grouping_cfg=None, shape_cfg=
         _log(logger, "computing the canopy height model")
         result["canopy"] = canopy_model(r["coords"], labels=r["labels"], height_above_ground=hag, offset=mean, **canopy_cfg).to_host()
         result["stand"] = stand_summary(result["canopy"], result.get("inventory"))
+    if light:
+        _log(logger, "computing the light model")
+        lm = light_model(r["coords"], dtm, r["labels"], offset=mean, **light_cfg)
+        result["light"] = lm.to_host()
+        if inventory:                                                                 # the tree columns from the model's own grid, last
+            result["inventory"].update(lm.tree_light(T=len(result["inventory"]["tree_id"])))
     if preview:
         _log(logger, "rendering the previews")
         shown = dict(result, coords=r["coords"], labels=r["labels"])
@@ -346,7 +360,8 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
     the inventory holds stem profiles; crown_profiles.npz (util.crown.write_crown_profiles) when it holds crown profiles; skeletons.npz
     (util.branches.write_skeletons) when it holds "skeleton"; cylinders.npz (util.wood.write_cylinders) when it holds "cylinders"; leafwood.npy
     (util.leafwood.write_leafwood) when it holds "leafwood"; canopy.npz and stand.json
-    (util.canopy.write_canopy, write_stand) when the result holds a canopy; preview/<name>.png (util.render.write_png) when it holds
+    (util.canopy.write_canopy, write_stand) when the result holds a canopy; light.npz (util.light.write_light) when it holds a light
+    model; preview/<name>.png (util.render.write_png) when it holds
     previews."""
     save_formats = list(save_formats)
     check_formats(save_formats)
@@ -416,6 +431,10 @@ def save_results(result, out_dir, plot_name, save_formats=("npz",), save_treewis
         os.makedirs(out_dir, exist_ok=True)
         write_canopy(os.path.join(out_dir, "canopy.npz"), result["canopy"])
         write_stand(os.path.join(out_dir, "stand.json"), result["stand"])
+    if "light" in result:
+        from .light import write_light
+        os.makedirs(out_dir, exist_ok=True)
+        write_light(os.path.join(out_dir, "light.npz"), result["light"])
     if "preview" in result:
         from .render import write_previews
         write_previews(os.path.join(out_dir, "preview"), result["preview"])
@@ -500,6 +519,9 @@ def parse_args(argv=None):
     ap.add_argument("--canopy", action="store_true", help="write canopy.npz (canopy height model, tree tops, grid metrics) and stand.json (implies --terrain)")
     from . import canopy as _canopy
     _canopy.add_arguments(ap)
+    ap.add_argument("--light", action="store_true", help="write light.npz (voxel grid, openness, effective LAI and gap fractions on a sensor grid) and add the light columns to tree_inventory.csv when it is written (implies --terrain)")
+    from . import light as _light
+    _light.add_arguments(ap)
     ap.add_argument("--preview", action="store_true", help="write preview/<name>.png: the segmented cloud from the top and the south, heights, the contact sheet of the trees, and the DTM, CHM and wood flags where they are computed")
     from . import render as _render
     _render.add_arguments(ap, "preview-")
@@ -510,6 +532,7 @@ def parse_args(argv=None):
         _stem.check_params(_stem.params_of(a))
         _crown.check_params(_crown.params_of(a))
         _canopy.check_params(_canopy.params_of(a))
+        _light.check_params(_light.params_of(a))
         _branches.check_params(_branches.params_of(a))
         _wood.check_params(_wood.params_of(a))
         _leafwood.check_params(_leafwood.params_of(a))
@@ -555,11 +578,11 @@ def main(argv=None):
                     tau_vert=a.tau_vert, tau_off=a.tau_off)
     shape = dict(SHAPE_CFG, alpha=a.alpha, buffer_size_to_determine_edge_trees=a.edge_buffer, outer_remove=a.outer_remove)
     with torch.no_grad():
-        from . import branches as _branches, canopy as _canopy, crown as _crown, leafwood as _leafwood, render as _render, stem as _stem, terrain as _terrain, wood as _wood
+        from . import branches as _branches, canopy as _canopy, crown as _crown, leafwood as _leafwood, light as _light, render as _render, stem as _stem, terrain as _terrain, wood as _wood
         from .inventory import params_of
         res = segment_forest(points, model, sample, grouping, shape, a.return_type, logger, return_pointwise=a.save_pointwise,
                              inventory=a.inventory, inventory_cfg=params_of(a) if a.inventory or a.stem or a.crown or a.branches or a.wood or a.leafwood else None,
-                             terrain=a.terrain, terrain_cfg=_terrain.params_of(a) if a.terrain or a.canopy else None,
+                             terrain=a.terrain, terrain_cfg=_terrain.params_of(a) if a.terrain or a.canopy or a.light else None,
                              stem=a.stem, stem_cfg=_stem.params_of(a) if a.stem else None,
                              crown=a.crown, crown_cfg=_crown.params_of(a) if a.crown else None,
                              canopy=a.canopy, canopy_cfg=_canopy.params_of(a) if a.canopy else None,
@@ -567,7 +590,8 @@ def main(argv=None):
                              wood=a.wood, wood_cfg=_wood.params_of(a) if a.wood else None,
                              leafwood=a.leafwood, leafwood_cfg=_leafwood.params_of(a) if a.leafwood else None,
                              leafwood_scales=a.leafwood_scales, leafwood_scales_min=a.leafwood_scales_min,
-                             preview=a.preview, preview_cfg=_render.params_of(a, "preview-") if a.preview else None)
+                             preview=a.preview, preview_cfg=_render.params_of(a, "preview-") if a.preview else None,
+                             light=a.light, light_cfg=_light.params_of(a) if a.light else None)
     plot_name = os.path.splitext(os.path.basename(a.forest))[0]
     save_results(res, a.out, plot_name, a.formats, save_treewise=not a.no_treewise, save_pointwise=a.save_pointwise)
     cats = np.bincount(res["categories"], minlength=3)
