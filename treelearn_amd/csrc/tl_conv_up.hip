@@ -13,6 +13,10 @@
 // 64-B view) 78 -> 117 -- scattered 64-B row writes cost more than the gather form's parent fetches, which hit L2; with the weights read
 // from L2 per tile (they do not fit the LDS) 128 -> 96 58 -> 154 and 160 -> 128 46 -> 214.  So: one shape, the one with wide rows and two
 // views; the others stay on the gather forms.
+// (These timings predate the pass at the end of the kernel that writes zeros to fine rows without a parent: it reads the one-hot table once
+// more, 32 B per fine row.  Alone, on a synthetic level of the config-2 sizes (254 417 -> 1 105 126 rows, two 128-B views, both builds
+// alternated on one box, medians of 9 windows of 20 launches): 99.6 / 100.2 us without the pass, 108.4 / 108.3 us with it; bench.py's
+// config-2 step did not move, ratio 1.0001.)
 #include "tl_conv_internal.h"
 #include <atomic>
 
@@ -98,6 +102,24 @@ __global__ void __launch_bounds__(WAVES * 64) k_conv_up(ConvP p, const int32_t* 
       for (int s_ = 0; s_ < KS; ++s_) A[s_] = An[s_];
 #pragma unroll
       for (int k = 0; k < K; ++k) { ch[k][0] = chn[k][0]; ch[k][1] = chn[k][1]; }
+    }
+  }
+  // Fine rows WITHOUT a parent (a cell whose parent lies outside the coarse level's spatial shape is dropped by the stride-2 conv: odd
+  // extents) are no coarse row's child, so nothing above wrote them.  The gather forms store epi(0) there; so does this pass over the
+  // one-hot table [K][n_out] (32 B per fine row, coalesced per tap): a row with no tap present gets zeros through every view.
+  {
+    const int32_t* __restrict__ tab = p.table;
+    const int64_t nthr = (int64_t)gridDim.x * (WAVES * 64);
+    for (int64_t r = (int64_t)blockIdx.x * (WAVES * 64) + tid; r < p.n_out; r += nthr) {
+      int all = -1;                                    // stays negative while every tap of the row is absent (-1)
+#pragma unroll
+      for (int k = 0; k < K; ++k) all &= tab[(int64_t)k * p.n_out + r];
+      if (all < 0) {
+        for (int c0 = 0; c0 < NBO * 32; c0 += 8) {
+          float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+          epi_views8<true>(p, r, c0, z);
+        }
+      }
     }
   }
 }
