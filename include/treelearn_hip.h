@@ -629,8 +629,11 @@ int tl_hdbscan_prim_order_host(const int32_t* e_src, const int32_t* e_dst, const
 int tl_knn_vote(const float* ref_xyz, const int64_t* ref_label, int64_t nr, const float* q_xyz, int64_t nq, int k,
                 int64_t* out_label, tl_stream_t stream);
 /* The same vote over a uniform cell grid (exact; bit-identical to tl_knn_vote): the caller bins the reference points
- * (cell = floor((p - lo) * (1.0f / h)) per axis in fp32, key = (cx * dims[1] + cy) * dims[2] + cz), sorts them by key and passes the
+ * (cell = floor(((double)p - (double)lo) * (double)(1.0f / h)) per axis, each operation rounded on its own,
+ * key = (cx * dims[1] + cy) * dims[2] + cz), sorts them by key and passes the
  * sorted coordinates / labels / ORIGINAL indices, the ncells distinct keys ascending and their row ranges cell_start[ncells + 1].
+ * 1 <= dims[a] <= 2^20 per axis, else TL_ERR_ARG: the ring bound is argued for fp64 binning over at most 2^20 cells (fp32 binning
+ * moved cell borders by more than the bound's 0.1 % margin from about 2 * 10^4 cells per axis on).
  * A query walks Chebyshev rings of cells until its k-th best distance beats anything an unvisited ring can hold; ties are broken
  * by (distance, original index) as in the brute-force form.  O(nq * points near the query) instead of O(nq * nr). */
 int tl_knn_vote_grid(const float* ref_sorted_xyz, const int64_t* ref_sorted_label, const int64_t* ref_sorted_index, int64_t nr,

@@ -91,14 +91,14 @@ __global__ void __launch_bounds__(256) k_group_mean(const float* __restrict__ sr
       const int64_t i = base + j, key = keys[i];
       int64_t cnt = 0;
       for (int64_t q = i; q < n && keys[q] == key; ++q) ++cnt;
-      const double inv = 1.0 / (double)cnt;
+      const double dcnt = (double)cnt;                         // divide, as groupby().mean() does: acc * (1 / cnt) truncates 49 equal labels L to L - 1
       for (int c0 = 0; c0 < C; c0 += 8) {                      // eight columns at a time: bounded registers, rows re-read from L2
         double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int64_t q = i; q < i + cnt; ++q) {
           const float* row = src + perm[q] * (int64_t)C + c0;
           for (int c = 0; c < 8; ++c) if (c0 + c < C) acc[c] += (double)row[c];
         }
-        for (int c = 0; c < 8; ++c) if (c0 + c < C) mean[grp * C + c0 + c] = acc[c] * inv;
+        for (int c = 0; c < 8; ++c) if (c0 + c < C) mean[grp * C + c0 + c] = acc[c] / dcnt;
       }
       first_idx[grp] = perm[i];
       ++grp;

@@ -39,7 +39,11 @@ def ensemble(coords, semantic_scores, semantic_labels, offset_predictions, offse
     M = int(m.item())
     mean = mean[:M]; first = first[:M]
     parts = torch.split(mean, widths, dim=1)
-    out_coords = (q[first] / 100.0).float()                       # the rounded coordinates themselves
+    # the rounded coordinates themselves: np.round(x, 2) divides rint(x * 100) by 100 in float32.  A tensor divided by a Python scalar is
+    # multiplied by its reciprocal on the device (one ulp off for some values), so divide by a tensor, in float64: rounding the float64
+    # quotient to float32 gives the correctly rounded float32 quotient (53 >= 2 * 24 + 2 bits)
+    qf = q[first].double()
+    out_coords = (qf / torch.full_like(qf, 100.0)).float()
     if return_device:            # same eight results as device tensors (the 32 backbone columns are the bulk of the D2H otherwise)
         f32 = lambda t: t.float()                                                            # noqa: E731
         i64 = lambda t: t[:, 0].to(torch.int64)                                              # noqa: E731
@@ -58,7 +62,10 @@ GRID_KNN_MIN_REF = 4096          # below this the brute-force kernel is as fast
 def knn_vote(ref, lab, qry, k, force=None):
     """Majority label of the k nearest reference points of every query (device tensors: ref f32[nr,3], lab i64[nr], qry f32[nq,3]).
     Large reference sets go through the cell grid (tl_knn_vote_grid: exact, bit-identical to the brute-force tl_knn_vote);
-    `force` = "grid" / "brute" pins the path (tests)."""
+    `force` = "grid" / "brute" pins the path (tests).
+    The grid has at most 2^20 cells per axis and its cells are binned in float64 on the float32 coordinates: the two roundings of
+    (p - lo) * inv_h then move a cell border by less than 2^-32 of a cell, far inside the 0.1 % margin of the kernel's ring bound.
+    (Binned in float32, borders moved by 0.4 % of a cell at 10^5 cells per axis and a nearer point two rings out could be missed.)"""
     L = _hip.lib()
     nr, nq = ref.shape[0], qry.shape[0]
     if k < 1 or k > nr:                                                # sklearn's rule (and message) for the classifier / NearestNeighbors the reference uses
@@ -73,10 +80,11 @@ def knn_vote(ref, lab, qry, k, force=None):
     lo = ref.min(dim=0).values
     ext = (ref.max(dim=0).values - lo).clamp_min(1e-3)
     lo_h, ext_h = lo.cpu().numpy().astype(np.float32), ext.cpu().numpy().astype(np.float64)
-    # cell edge: about 8 reference points per cell of the bounding box, at least 5 cm, at most 2^20 cells per axis
-    h = np.float32(max(0.05, float((ext_h.prod() * 8.0 / nr) ** (1.0 / 3.0)), float(ext_h.max()) / (1 << 20)))
+    # cell edge: about 8 reference points per cell of the bounding box, at least 5 cm, at most 2^20 cells per axis (the 16 spare cells
+    # absorb the float32 roundings of h and 1 / h: tl_knn_vote_grid refuses dims beyond 2^20)
+    h = np.float32(max(0.05, float((ext_h.prod() * 8.0 / nr) ** (1.0 / 3.0)), float(ext_h.max()) / ((1 << 20) - 16)))
     inv_h = np.float32(1.0) / h                                        # the kernel computes 1.0f / h the same way
-    cell = ((ref - lo) * float(inv_h)).floor().to(torch.int64)
+    cell = ((ref.double() - lo.double()) * float(inv_h)).floor().to(torch.int64)     # float64, separate roundings: as knn_cell in the kernel
     dims = (cell.max(dim=0).values + 1).cpu().numpy().astype(np.int64)
     key = (cell[:, 0] * int(dims[1]) + cell[:, 1]) * int(dims[2]) + cell[:, 2]
     skey, order = torch.sort(key, stable=True)
