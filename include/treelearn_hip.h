@@ -571,6 +571,38 @@ int tl_sor_keep(const double* avg, int64_t n, double std_ratio, uint8_t* keep, d
 int tl_radius_count(const double* xyz_sorted, const int64_t* keys_sorted, const int64_t* perm, int64_t n, const double lo[3], double h,
                     const int32_t dims[3], double radius, int32_t* count, tl_stream_t stream);
 
+/* ------------------------------------------------------------------ two epochs of one plot (csrc/tl_change.hip)
+ * The hot path of rigid registration (ICP), cloud-to-cloud distances and tree matching between two scans.  The semantics are the
+ * project's own; tests/change_restatement.py states them in numpy and is the specification.  All arithmetic is f64 without fma
+ * contraction, every operation rounded on its own; f32 queries are widened first.
+ *
+ * Queries: q = f32 (dtype_f64 = 0) or f64 (dtype_f64 = 1) [nq, >= 3] with a row stride of ld elements (ld >= 3), in their original
+ *   order.  T = HOST pointer to 12 doubles, a row-major 3 x 4 rigid transform handed to the kernel by value; NULL = identity.
+ *   moved query  x'_a = ((T[a][0]*x + T[a][1]*y) + T[a][2]*z) + T[a][3]  per axis a.
+ * Reference: binned and sorted exactly as for the outlier section above (tl_outlier_keys, one sort): xyz_sorted f64[nr,3],
+ *   keys_sorted, perm i64[nr] = original row of sorted row, and the grid lo, h, dims.
+ *
+ * tl_cross_nn: nn i64[nq], d2 f64[nq]: over the reference rows j with d2(i, j) = (dx*dx + dy*dy) + dz*dz < max_dist * max_dist
+ *   (strict) the smallest d2 and the ORIGINAL row that has it; among equal d2 the smaller original row.  No such row, or a moved
+ *   query that is not finite: nn = -1, d2 = +inf.  The moved query may lie anywhere (its cell index is clamped in f64; up to one cell
+ *   outside the grid it still sees the border cells).  Needs h >= 1.0001 * max_dist (else TL_ERR_ARG): the ball then lies inside the
+ *   27 cells around the query's own.  nr = 0 writes -1 / +inf for every query (the reference pointers and the grid are not looked
+ *   at); nq = 0 returns TL_OK without a launch.  The results do not depend on the grid, the launch or the reference's row order.
+ * tl_rigid_sums: sums f64[17] (device) of one ICP step over the rows i with 0 <= nn[i] < nr and d2[i] < reject2.  ref f64[nr,3] is
+ *   the reference in ORIGINAL row order, c[3] (host) a centre that keeps the products small.  With a = x'_i - c and b = ref[nn[i]] - c
+ *   a row contributes 1.0, a (3), b (3), the outer product a b^T row-major (9, each a single multiply) and d2[i]; any other row
+ *   contributes +0.0 to all 17.  Every sum is a fixed tree: rows in chunks of 2048 in row order, within a chunk
+ *   s[i] += s[i + stride] for stride 1024 .. 1 with missing rows at +0.0, then the same tree over the chunk partials, 2048 at a
+ *   time, until one is left.  No atomics: the same bits on every run and for any launch geometry.  nq = 0 gives 17 zeros.
+ *   ws f64[tl_rigid_sums_ws_doubles(nq)].
+ * Null or misaligned pointers and bad sizes are refused (TL_ERR_ARG) before anything else. */
+int tl_cross_nn(const double* xyz_sorted, const int64_t* keys_sorted, const int64_t* perm, int64_t nr, const double lo[3], double h,
+                const int32_t dims[3], const void* q, int dtype_f64, int64_t ld, int64_t nq, const double* T, double max_dist, int64_t* nn,
+                double* d2, tl_stream_t stream);
+int64_t tl_rigid_sums_ws_doubles(int64_t nq);
+int tl_rigid_sums(const void* q, int dtype_f64, int64_t ld, int64_t nq, const double* T, const int64_t* nn, const double* d2, const double* ref,
+                  int64_t nr, const double c[3], double reject2, double* sums, double* ws, tl_stream_t stream);
+
 /* ------------------------------------------------------------------ clustering
  * Replaces sklearn DBSCAN(eps, min_samples=2) in group_dbscan (tree_learn/util/pipeline.py:173-180):
  * connected components of the eps-graph on 2-D points; isolated points = -1; component labels

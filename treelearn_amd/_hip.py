@@ -259,6 +259,10 @@ PROTOTYPES = {
     "tl_sor_ws_doubles": (_i64, [_i64]),
     "tl_sor_keep": (_i32, [_vp, _i64, _c.c_double, _vp, _vp, _vp, _vp]),
     "tl_radius_count": (_i32, [_vp, _vp, _vp, _i64, _c.c_double * 3, _c.c_double, _I3, _c.c_double, _vp, _vp]),
+    "tl_cross_nn": (_i32, [_vp, _vp, _vp, _i64, _c.c_double * 3, _c.c_double, _I3, _vp, _i32, _i64, _i64, _c.POINTER(_c.c_double), _c.c_double, _vp, _vp,
+                           _vp]),
+    "tl_rigid_sums_ws_doubles": (_i64, [_i64]),
+    "tl_rigid_sums": (_i32, [_vp, _i32, _i64, _i64, _c.POINTER(_c.c_double), _vp, _vp, _vp, _i64, _c.c_double * 3, _c.c_double, _vp, _vp, _vp]),
     "tl_ring_classify": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 TL_EVAL_XY, TL_EVAL_Z = 0, 1

@@ -20,33 +20,16 @@
 // ascending by lane (k <= 64 = the wave width: no per-lane list, a handful of registers); a candidate below the k-th best is inserted
 // with one ballot, one popcount and one lane shift.
 #include "tl_common.h"
+#include "tl_morton.h"                                 // the grid, the Morton key, the 27-cell range search
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int kBlock = 256, kWaves = kBlock / 64;
-constexpr int kBits = 21;                              // cells per axis: 2^21
 constexpr int kMaxK = 64;
 constexpr int kChunk = 2048;                           // rows per partial of the two cloud sums (fixed: the sums do not depend on the grid)
 constexpr double kInf = 1e300;
-
-struct Grid {
-  double lo[3]; double h;
-  int dims[3];                                         // cells per axis at level 0
-};
-
-// bits of v (21 used) spread to every third position
-__host__ __device__ __forceinline__ uint64_t spread3(uint64_t v) {
-  v &= 0x1fffffull;
-  v = (v | v << 32) & 0x1f00000000ffffull;
-  v = (v | v << 16) & 0x1f0000ff0000ffull;
-  v = (v | v << 8) & 0x100f00f00f00f00full;
-  v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-  v = (v | v << 2) & 0x1249249249249249ull;
-  return v;
-}
-__device__ __forceinline__ uint64_t morton(int x, int y, int z) { return spread3((uint64_t)x) << 2 | spread3((uint64_t)y) << 1 | spread3((uint64_t)z); }
 
 __device__ __forceinline__ int cell_of(double p, double lo, double h) { return (int)floor((p - lo) / h); }
 
@@ -61,29 +44,6 @@ __global__ void __launch_bounds__(kBlock) k_keys(const double* __restrict__ xyz,
     if (bad) { *err = 1; keys[i] = 0; continue; }
     keys[i] = (int64_t)morton(c[0], c[1], c[2]);
   }
-}
-
-// first row in [0, n) whose key is >= key (n when none); keys are below 2^63, key may be 2^63
-__device__ __forceinline__ int64_t lower_bound(const int64_t* __restrict__ keys, int64_t n, uint64_t key) {
-  int64_t a = 0, b = n;
-  while (a < b) { const int64_t m = (a + b) >> 1; if ((uint64_t)keys[m] < key) a = m + 1; else b = m; }
-  return a;
-}
-
-// lane l < 27: the row range of the level-s cell (qc + offset l) of the sorted array; empty outside the grid and for lanes >= 27
-__device__ __forceinline__ void cell_range(const int64_t* __restrict__ keys, int64_t n, const Grid& g, const int qc[3], int s, int lane,
-                                           int64_t* start, int64_t* end) {
-  *start = 0; *end = 0;
-  if (lane >= 27) return;
-  const int d[3] = {lane / 9 - 1, (lane / 3) % 3 - 1, lane % 3 - 1};
-  int c[3];
-  for (int a = 0; a < 3; ++a) {
-    c[a] = (qc[a] >> s) + d[a];
-    if (c[a] < 0 || c[a] > ((g.dims[a] - 1) >> s)) return;
-  }
-  const uint64_t m = morton(c[0], c[1], c[2]);
-  *start = lower_bound(keys, n, m << (3 * s));
-  *end = lower_bound(keys, n, (m + 1) << (3 * s));       // s = 21: m = 0 and 1 << 63 is above every key
 }
 
 __device__ __forceinline__ double dist2(const double* __restrict__ xyz, int64_t j, double x, double y, double z) {
@@ -221,16 +181,6 @@ __global__ void __launch_bounds__(kBlock) k_keep(const double* __restrict__ avg,
 __global__ void k_keep_none(uint8_t* __restrict__ keep, int64_t n, double* __restrict__ thr_out) {
   if (threadIdx.x == 0) *thr_out = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += blockDim.x) keep[i] = 0;
-}
-
-bool make_grid(const double lo[3], const int32_t dims[3], double h, Grid* g) {
-  if (!lo || !dims || !(h > 0.0)) return false;
-  for (int a = 0; a < 3; ++a) {
-    if (dims[a] < 1 || dims[a] > (1 << kBits)) return false;
-    g->lo[a] = lo[a]; g->dims[a] = dims[a];
-  }
-  g->h = h;
-  return true;
 }
 
 unsigned wave_grid(int64_t n) {                          // one wavefront per row, at most 256 CUs x 8 blocks
